@@ -19,7 +19,18 @@ ranks / max rank time ("scaling": "weak").  Under torchrun the ranks come from
 the environment; `--gpus N` without torchrun starts the N rank processes
 itself, before anything touches the GPU.
 
-Also reported (rank 0):
+A plain run sets up, warms up, times `--steps` steps and prints the result
+line (`value`, `ms_per_step` = milliseconds per timed step, the configuration).
+`--dump-outputs DIR` also writes what the last timed step computed: a fixed,
+seeded sample of the output ciphertext words (all of them when they fit) as
+float64 DIR/out.npy (exact below 2^53, which every modulus of the default
+prime set is) and DIR/out_lo32.npy (the same words' low 32 bits, exact for
+any prime size); rank r of an N > 1 run writes its shard's sample as
+out.rank<r>.npy and out_lo32.rank<r>.npy.  The inputs
+and the keys come from fixed seeds, so two runs with the same arguments
+compute the same words.
+
+With --full, also reported (rank 0):
   roofline      - the dominant kernel: SURVEY 8(d)'s algorithmic bytes per op
                   (2 ct in, 1 ct out at L-1, key / batch) x the pairs one launch
                   processes, / its average launch time (HIP events on the
@@ -90,6 +101,13 @@ def parse(argv=None):
     ap.add_argument("--check-shards", action="store_true",
                     help="after the timed steps, gather every rank's output shard and compare it bit for bit "
                          "with one rank's run of the whole global batch (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything listed under 'With --full' above (the "
+                         "instrumented pass and roofline, the 60-bit primes, config 5, NTT, gemv, CSTR and CPU legs; "
+                         "each --no-* option drops its leg)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (a fixed, seeded sample "
+                         "of the output ciphertext words) as float64 DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -295,6 +313,26 @@ def timed(fn, steps, warmup, sync, barrier):
     torch.cuda.synchronize()
     barrier()
     return time.perf_counter() - t0
+
+
+DUMP_WORDS, DUMP_SEED = 1 << 21, 0x48454354520002  # --dump-outputs: two float64 arrays of 16 MiB at most
+
+
+def dump_outputs(out, path, rank, world):
+    """--dump-outputs: the words of `out` (he_mul_rescale_batch's output
+    ciphertexts as the last timed step left them) at DUMP_WORDS positions drawn
+    once from DUMP_SEED, or all of them when there are no more than that; see
+    the module docstring for the two files."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    if out.numel() > DUMP_WORDS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, out.numel(), DUMP_WORDS))
+        out = out[torch.from_numpy(idx).to(out.device)]
+    words = out.cpu().numpy().view(np.uint64)
+    tag = "" if world == 1 else f".rank{rank}"
+    np.save(os.path.join(path, f"out{tag}.npy"), words.astype(np.float64))
+    np.save(os.path.join(path, f"out_lo32{tag}.npy"), (words & np.uint64(0xFFFFFFFF)).astype(np.float64))
 
 
 def pmc_profile(workload, pairs_per_launch):
@@ -907,31 +945,32 @@ def main():
     elapsed = max(rank_times)
     value = world * B * args.steps / elapsed
     ms_per_step = 1e3 * elapsed / args.steps
-
-    # instrumented pass (same steps): per-kernel device time from HIP events on
-    # the engine stream, streamed bytes per launch from the library -- with
-    # the batch as one chunk on one stream, so each kernel's launch time is
-    # its own (two streams overlap the kernels of the two sub-chunks)
-    eng.lib.gpqhe_set_streams(1)
-    eng.prof_enable(True)
-    ti0 = time.perf_counter()
-    for _ in range(args.steps):
-        mb.step()
-    eng.sync()
-    ti1 = time.perf_counter()
-    stats = eng.prof_collect()
-    eng.prof_enable(False)
-    eng.lib.gpqhe_set_streams(args.streams)
-    step_s = (ti1 - ti0) / args.steps
-    launches_per_step = stats[max(stats, key=lambda k: stats[k][1])][0] / args.steps
-    pairs_per_launch = int(round(B / launches_per_step))
+    if args.dump_outputs:
+        dump_outputs(mb.out, args.dump_outputs, rank, world)
     workload = (f"ct x ct mult + relin + rescale, N=2^{logn}, L={L}, K={mb.K}, dnum={mb.dnum}, "
                 f"primes {args.q0_bits}/50/{args.p_bits} bits, batch={B} pairs per GPU")
 
+    if args.full:
+        # instrumented pass (same steps): per-kernel device time from HIP events on
+        # the engine stream, streamed bytes per launch from the library -- with
+        # the batch as one chunk on one stream, so each kernel's launch time is
+        # its own (two streams overlap the kernels of the two sub-chunks)
+        eng.lib.gpqhe_set_streams(1)
+        eng.prof_enable(True)
+        ti0 = time.perf_counter()
+        for _ in range(args.steps):
+            mb.step()
+        eng.sync()
+        ti1 = time.perf_counter()
+        stats = eng.prof_collect()
+        eng.prof_enable(False)
+        eng.lib.gpqhe_set_streams(args.streams)
+        step_s = (ti1 - ti0) / args.steps
+        launches_per_step = stats[max(stats, key=lambda k: stats[k][1])][0] / args.steps
+        pairs_per_launch = int(round(B / launches_per_step))
+
     result = None
     if rank == 0:
-        kernels = {k: {"launches": v[0], "avg_us": v[1] / v[0], "share": v[1] / (1e6 * step_s * args.steps),
-                       "streamed_GBs": v[2] / v[1] / 1e3} for k, v in sorted(stats.items(), key=lambda kv: -kv[1][1])}
         alg = mb.alg_bytes()
         result = {
             "metric": "ct×ct+relin/sec at N=2^16, L=8 RNS primes; encrypted CSTR-MPC steps/sec",
@@ -953,7 +992,6 @@ def main():
             "config": {"workload": workload,
                        "batch_per_gpu": B, "logn": logn, "nlimbs": L, "nspecial": mb.K,
                        "dnum": mb.dnum, "prime_bits": {"q0": args.q0_bits, "qi": 50, "p": args.p_bits},
-                       "pairs_per_launch": pairs_per_launch,
                        "streams": args.streams,
                        "parallelism": f"batch-sharded x{world}"},
             "per_gpu_value": value / world,
@@ -961,10 +999,14 @@ def main():
             "op_roofline": {"alg_bytes_per_op": alg, "achieved_GBs": alg * value / world / 1e9,
                             "frac": alg * value / world / 1e9 / HBM_PEAK_GBS,
                             "us_per_op": 1e6 * world / value},
-            "roofline": roofline(stats, step_s * args.steps, mb, workload, pairs_per_launch),
-            "kernels": kernels,
-            "instrumented_ms_per_step": 1e3 * step_s,
         }
+    if rank == 0 and args.full:
+        result["config"]["pairs_per_launch"] = pairs_per_launch
+        result["roofline"] = roofline(stats, step_s * args.steps, mb, workload, pairs_per_launch)
+        result["kernels"] = {k: {"launches": v[0], "avg_us": v[1] / v[0], "share": v[1] / (1e6 * step_s * args.steps),
+                                 "streamed_GBs": v[2] / v[1] / 1e3}
+                             for k, v in sorted(stats.items(), key=lambda kv: -kv[1][1])}
+        result["instrumented_ms_per_step"] = 1e3 * step_s
         # the op's two design floors beside the measured time: the five
         # kernels' VALU instructions at full issue (PMC profile) and their design
         # HBM traffic at the 8 TB/s peak; the frac the op could reach at each
@@ -991,7 +1033,7 @@ def main():
         if rank == 0:
             result["shard_check"] = chk
 
-    if args.alt_bits and args.alt_bits != args.q0_bits:
+    if args.full and args.alt_bits and args.alt_bits != args.q0_bits:
         # the conventional prime sizes (60-bit q0 and special primes: the
         # integer butterflies on those limbs), same op, batch and harness
         alt = MulBatch(stream, logn, L, dnum, args.alt_bits, args.alt_bits, 0, B, rank * B, KEY_SEED)
@@ -1016,7 +1058,7 @@ def main():
         alt.close()
         barrier()
 
-    if not args.no_c5:
+    if args.full and not args.no_c5:
         # config 5: n = 2^17, L = 12 (dnum 3, K 4), each rank its own shard of
         # the global batch; the headline's prime sizes (q0 and P of
         # --q0-bits / --p-bits: every modulus below 2^51) and the conventional
@@ -1067,7 +1109,7 @@ def main():
                 main5["value_60bit"] = alt5["value"]
                 main5["alt_primes"] = alt5
 
-    if not args.no_gemv:
+    if args.full and not args.no_gemv:
         g = gemv_leg(args, stream, rank, world, red_dev, barrier, backend)
         if rank == 0:
             result["gemv"] = g
@@ -1076,9 +1118,9 @@ def main():
             if rank == 0:
                 result["config5"]["hempc_gemv"] = g5
 
-    if rank == 0 and world == 1 and not args.no_cstr:
+    if args.full and rank == 0 and world == 1 and not args.no_cstr:
         result["cstr"] = cstr_loop(args.cstr_steps)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         result["cpu_baseline"] = cpu_baseline(args, logn, L, dnum)
     if rank == 0:
         print(json.dumps(result), flush=True)

@@ -13,7 +13,7 @@ fi
 i=0
 for setting in "$@"; do
   i=$((i + 1))
-  env $setting timeout -k 10 300 python bench.py --no-cpu --no-cstr ${BENCH_ARGS:-} > $OUT/bench_$i.log 2>&1 || { echo "bench failed ($setting)"; tail -30 $OUT/bench_$i.log; exit 1; }
+  env $setting timeout -k 10 300 python bench.py --full --no-cpu --no-cstr ${BENCH_ARGS:-} > $OUT/bench_$i.log 2>&1 || { echo "bench failed ($setting)"; tail -30 $OUT/bench_$i.log; exit 1; }
   echo "== $setting"
   python scripts/ab_summary.py $OUT/bench_$i.log
 done

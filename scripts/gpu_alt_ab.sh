@@ -7,7 +7,7 @@ cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/${RUN:-alt_ab}; mkdir -p $OUT
 env $2 timeout -k 10 400 python -u -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "mul_rescale" --timeout 200 --timeout-method thread > $OUT/pytest.log 2>&1 || { tail -20 $OUT/pytest.log; exit 1; }
 tail -1 $OUT/pytest.log
-B="python bench.py --steps 5 --warmup 1 --no-cpu --no-cstr --no-ntt --no-c5 --alt-bits 0 ${BENCH_ARGS}"
+B="python bench.py --full --steps 5 --warmup 1 --no-cpu --no-cstr --no-ntt --no-c5 --alt-bits 0 ${BENCH_ARGS}"
 for r in 1 2; do
   i=0
   for setting in "$@"; do

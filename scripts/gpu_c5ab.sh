@@ -8,7 +8,7 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 OUT=gpurun_out/${RUN:-c5ab}
 mkdir -p $OUT
-B="python bench.py --steps 6 --warmup 1 --no-cpu --no-cstr --no-ntt --no-c5 --alt-bits 0 --logn 17 --nlimbs 12 --dnum 3 --nspecial 4 --batch 64"
+B="python bench.py --full --steps 6 --warmup 1 --no-cpu --no-cstr --no-ntt --no-c5 --alt-bits 0 --logn 17 --nlimbs 12 --dnum 3 --nspecial 4 --batch 64"
 for r in $(seq 1 ${ROUNDS:-2}); do
   timeout -k 10 240 $B > $OUT/bench_base_$r.log 2>&1 || exit 1
   [ -n "$C5_60" ] && { timeout -k 10 240 $B --q0-bits 60 --p-bits 60 > $OUT/bench_base60_$r.log 2>&1 || exit 1; }

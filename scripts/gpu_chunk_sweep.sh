@@ -9,7 +9,7 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 OUT=gpurun_out/${RUN:-sweep}
 mkdir -p $OUT
-B="python bench.py --steps 10 --warmup 2 --no-cpu --no-cstr --no-ntt --no-c5 --alt-bits 0"
+B="python bench.py --full --steps 10 --warmup 2 --no-cpu --no-cstr --no-ntt --no-c5 --alt-bits 0"
 for r in $(seq 1 ${ROUNDS:-1}); do
   for c in ${CHUNKS:-256 128 64 32 16 8}; do
     GPQHE_CHUNK=$c timeout -k 10 300 $B > $OUT/bench_nt_c${c}_$r.log 2>&1 || exit 1

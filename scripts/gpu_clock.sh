@@ -6,7 +6,7 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 OUT=gpurun_out/${RUN:-clock}
 mkdir -p $OUT
-B="python bench.py --steps 3 --warmup 1 --no-cpu --no-cstr --no-ntt --alt-bits 0"
+B="python bench.py --full --steps 3 --warmup 1 --no-cpu --no-cstr --no-ntt --alt-bits 0"
 timeout -s KILL 120 rocprofv3 --pmc GRBM_GUI_ACTIVE GRBM_COUNT -d $OUT/clk -o clk --output-format csv -- $B > $OUT/clk.log 2>&1 || exit 1
 python - $OUT/clk/clk_counter_collection.csv <<'PY'
 import csv, collections, sys

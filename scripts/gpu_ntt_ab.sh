@@ -13,7 +13,7 @@ for r in 1 2; do
   i=0
   for setting in "$@"; do
     i=$((i + 1))
-    env $setting timeout -k 10 300 python bench.py --steps 3 --warmup 1 --no-cpu --no-cstr --no-c5 --alt-bits 0 > $OUT/bench_${i}_$r.log 2>&1 || { echo "bench failed ($setting)"; tail -30 $OUT/bench_${i}_$r.log; exit 1; }
+    env $setting timeout -k 10 300 python bench.py --full --steps 3 --warmup 1 --no-cpu --no-cstr --no-c5 --alt-bits 0 > $OUT/bench_${i}_$r.log 2>&1 || { echo "bench failed ($setting)"; tail -30 $OUT/bench_${i}_$r.log; exit 1; }
     echo "== $setting round $r"; python scripts/ab_summary.py $OUT/bench_${i}_$r.log | grep -i "ntt\|ct-mult"
   done
 done

@@ -8,12 +8,12 @@ export TMPDIR=/tmp
 OUT=gpurun_out/${RUN:-prof}
 mkdir -p $OUT
 if [ -z "$NO_FULL" ]; then
-  timeout -k 10 600 python bench.py > $OUT/bench_full.log 2>&1 || exit 1
+  timeout -k 10 600 python bench.py --full > $OUT/bench_full.log 2>&1 || exit 1
 fi
 # the kernel-trace pass runs the bench's own steps / warmup, so its mean launch
 # time is the one the bench line's roofline uses; PMC passes run short
-BK="python bench.py --steps 10 --warmup 2 --no-cpu --no-cstr --no-ntt --no-c5 --no-gemv --alt-bits 0 --streams 1"
-B="python bench.py --steps 3 --warmup 1 --no-cpu --no-cstr --no-ntt --no-c5 --no-gemv --alt-bits 0 --streams 1"
+BK="python bench.py --full --steps 10 --warmup 2 --no-cpu --no-cstr --no-ntt --no-c5 --no-gemv --alt-bits 0 --streams 1"
+B="python bench.py --full --steps 3 --warmup 1 --no-cpu --no-cstr --no-ntt --no-c5 --no-gemv --alt-bits 0 --streams 1"
 N="python scripts/prof_ntt.py 1024"
 # the gemv leg's workload (he_gemv_batch at the bench shape, 256 ciphertexts)
 GV="python scripts/gemv_time.py --set bench51 --count 256 --single 0 --rot 0"

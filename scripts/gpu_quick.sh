@@ -8,7 +8,7 @@ OUT=gpurun_out/${RUN:-quick}
 mkdir -p $OUT
 timeout -k 10 900 python -u -m pytest tests -x -q -m gpu --timeout 300 --timeout-method thread > $OUT/pytest.log 2>&1 || { echo "pytest failed"; tail -40 $OUT/pytest.log; exit 1; }
 tail -2 $OUT/pytest.log
-timeout -k 10 600 python bench.py --no-cpu "$@" > $OUT/bench.log 2>&1 || { echo "bench failed"; tail -30 $OUT/bench.log; exit 1; }
+timeout -k 10 600 python bench.py --full --no-cpu "$@" > $OUT/bench.log 2>&1 || { echo "bench failed"; tail -30 $OUT/bench.log; exit 1; }
 python - $OUT/bench.log <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

@@ -13,5 +13,5 @@ if [ -z "$SKIP_TESTS" ]; then
   timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { echo "smoke failed"; cat $OUT/smoke.log; exit 1; }
   tail -1 $OUT/smoke.log
 fi
-timeout -k 10 600 python bench.py --no-cpu > $OUT/bench.log 2>&1 || { echo "bench failed"; tail -30 $OUT/bench.log; exit 1; }
+timeout -k 10 600 python bench.py --full --no-cpu > $OUT/bench.log 2>&1 || { echo "bench failed"; tail -30 $OUT/bench.log; exit 1; }
 python scripts/ab_summary.py $OUT/bench.log 2>/dev/null | head -40

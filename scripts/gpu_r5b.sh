@@ -16,7 +16,7 @@ if [ -z "$NO_TIME" ]; then
   timeout -k 10 300 python scripts/gemv_time.py --set bench_d2 --count 64 > $OUT/gemv_win_d2.json 2>&1 || { cat $OUT/gemv_win_d2.json; exit 1; }
   tail -1 $OUT/gemv_generic_d2.json | cut -c1-300; tail -1 $OUT/gemv_win_d2.json | cut -c1-300
 fi
-timeout -k 10 600 python bench.py --no-cpu --no-cstr --no-ntt --no-c5 > $OUT/bench.log 2>&1 || { echo "bench failed"; tail -30 $OUT/bench.log; exit 1; }
+timeout -k 10 600 python bench.py --full --no-cpu --no-cstr --no-ntt --no-c5 > $OUT/bench.log 2>&1 || { echo "bench failed"; tail -30 $OUT/bench.log; exit 1; }
 python - $OUT/bench.log <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith('{"metric"')][-1])
@@ -31,7 +31,7 @@ for k, v in g.get("kernels", {}).items():
     print(f" 51 {k:28s} {v['launches']:4d} x {v['avg_us']:8.1f} us  {v['us_per_gemv']:6.2f} us/gemv")
 PY
 if [ -n "$PIPE_KT" ]; then
-  B="python bench.py --steps 10 --warmup 2 --no-cpu --no-cstr --no-ntt --no-c5 --no-gemv --alt-bits 0"
+  B="python bench.py --full --steps 10 --warmup 2 --no-cpu --no-cstr --no-ntt --no-c5 --no-gemv --alt-bits 0"
   GPQHE_SPLIT_PIPE=4 timeout -s KILL 240 rocprofv3 --kernel-trace --stats -d $OUT/kt_pipe4 -o kt_pipe4 --output-format csv -- $B > $OUT/kt_pipe4.log 2>&1 || exit 1
   timeout -s KILL 240 rocprofv3 --kernel-trace --stats -d $OUT/kt_pipe0 -o kt_pipe0 --output-format csv -- $B > $OUT/kt_pipe0.log 2>&1 || exit 1
 fi

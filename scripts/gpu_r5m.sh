@@ -8,7 +8,7 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 OUT=gpurun_out/${RUN:-r5m}
 mkdir -p $OUT
-B="python bench.py --no-cpu --no-cstr --no-ntt --no-c5 --no-gemv --alt-bits 0"
+B="python bench.py --full --no-cpu --no-cstr --no-ntt --no-c5 --no-gemv --alt-bits 0"
 VARS="0:0 2:0 2:8 2:16 4:8 0:8"
 for r in 1 2; do
   for v in $VARS; do
@@ -19,6 +19,6 @@ for r in 1 2; do
 done
 for v in 2:8 0:8; do
   p=${v%:*}; m=${v#*:}
-  GPQHE_SPLIT_PIPE=$p GPQHE_S2_MASK=$m timeout -s KILL 240 rocprofv3 --kernel-trace -d $OUT/kt_p${p}_m${m} -o kt --output-format csv -- python bench.py --steps 5 --warmup 1 --no-cpu --no-cstr --no-ntt --no-c5 --no-gemv --alt-bits 0 > $OUT/kt_p${p}_m${m}.log 2>&1 || { echo "trace $v failed"; exit 1; }
+  GPQHE_SPLIT_PIPE=$p GPQHE_S2_MASK=$m timeout -s KILL 240 rocprofv3 --kernel-trace -d $OUT/kt_p${p}_m${m} -o kt --output-format csv -- python bench.py --full --steps 5 --warmup 1 --no-cpu --no-cstr --no-ntt --no-c5 --no-gemv --alt-bits 0 > $OUT/kt_p${p}_m${m}.log 2>&1 || { echo "trace $v failed"; exit 1; }
   python scripts/kt_overlap.py $OUT/kt_p${p}_m${m} | head -30
 done

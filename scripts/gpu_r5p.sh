@@ -11,7 +11,7 @@ OUT=gpurun_out/${RUN:-r5p}
 mkdir -p $OUT
 timeout -k 10 600 python -u -m pytest tests/test_gpu_parity.py tests/test_gpu_rotations.py -x -v -m gpu -k "${TESTS_K:-m60}" --timeout 300 --timeout-method thread > $OUT/pytest.log 2>&1 || { echo "pytest failed"; tail -40 $OUT/pytest.log; exit 1; }
 tail -1 $OUT/pytest.log
-B="python bench.py --no-cpu --no-cstr --no-ntt --no-c5 --no-gemv --alt-bits 0"
+B="python bench.py --full --no-cpu --no-cstr --no-ntt --no-c5 --no-gemv --alt-bits 0"
 for r in 1 2; do
   for v in "60 60 2" "60 51 3" "51 51 3" "51 51 2"; do
     set -- $v

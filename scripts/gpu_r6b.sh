@@ -14,7 +14,7 @@ if [ -z "$NO_TESTS" ]; then
     > $OUT/pytest.log 2>&1
   rc=$?; echo "pytest exit $rc" >> $OUT/pytest.log; tail -5 $OUT/pytest.log; [ $rc -eq 0 ] || exit 1
 fi
-B="python bench.py --steps 10 --warmup 2 --no-cpu --no-cstr --no-ntt ${BENCH_ARGS}"
+B="python bench.py --full --steps 10 --warmup 2 --no-cpu --no-cstr --no-ntt ${BENCH_ARGS}"
 for r in $(seq 1 ${ROUNDS:-2}); do
   GPQHE_LIB=hectr_amd/lib_ab/libgpqhe.so timeout -k 10 400 $B > $OUT/bench_base_$r.log 2>&1 || { echo "base bench failed"; tail -5 $OUT/bench_base_$r.log; exit 1; }
   timeout -k 10 400 $B > $OUT/bench_new_$r.log 2>&1 || { echo "new bench failed"; tail -5 $OUT/bench_new_$r.log; exit 1; }
@@ -22,5 +22,5 @@ for r in $(seq 1 ${ROUNDS:-2}); do
 done
 python scripts/ab_summary.py $OUT > $OUT/summary.txt || true
 [ -n "$NO_TRACE" ] && exit 0
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt --output-format csv -- python bench.py --steps 10 --warmup 2 --no-cpu --no-cstr > $OUT/kt.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt --output-format csv -- python bench.py --full --steps 10 --warmup 2 --no-cpu --no-cstr > $OUT/kt.log 2>&1
 rc=$?; echo "rocprofv3 exit $rc" | tee -a $OUT/kt.log; [ $rc -eq 0 ] || exit 1

@@ -13,7 +13,7 @@ if [ -n "$TESTS" ]; then
   rc=$?; echo "pytest exit $rc" >> $OUT/pytest.log; tail -4 $OUT/pytest.log; [ $rc -eq 0 ] || exit 1
 fi
 NO_NTT=--no-ntt; [ -n "$NTT" ] && NO_NTT=""
-B="python bench.py --steps 10 --warmup 2 --no-cpu --no-cstr $NO_NTT ${BENCH_ARGS}"
+B="python bench.py --full --steps 10 --warmup 2 --no-cpu --no-cstr $NO_NTT ${BENCH_ARGS}"
 for r in $(seq 1 ${ROUNDS:-2}); do
   for v in ${LIBS:-new=hectr_amd/lib/libgpqhe.so}; do
     GPQHE_LIB=${v#*=} timeout -k 10 400 $B > $OUT/bench_${v%%=*}_$r.log 2>&1 || { echo "bench $v failed"; tail -5 $OUT/bench_${v%%=*}_$r.log; exit 1; }

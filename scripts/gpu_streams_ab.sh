@@ -6,7 +6,7 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 OUT=gpurun_out/${RUN:-streams_ab}
 mkdir -p $OUT
-B="python bench.py --steps 10 --warmup 2 --no-cpu --no-cstr --no-ntt --no-c5 ${ALT:---alt-bits 0}"
+B="python bench.py --full --steps 10 --warmup 2 --no-cpu --no-cstr --no-ntt --no-c5 ${ALT:---alt-bits 0}"
 for r in $(seq 1 ${ROUNDS:-3}); do
   for s in 1 2; do
     timeout -k 10 240 $B --streams $s > $OUT/bench_s${s}_$r.log 2>&1 || exit 1

@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/${RUN:-varab}
 mkdir -p $OUT
 VARS=${VARS:-$(ls hectr_amd/lib_var 2>/dev/null)}
-B="python bench.py --steps ${STEPS:-10} --warmup 2 --no-cpu --no-cstr ${LEGS:---no-ntt --no-c5} --alt-bits ${ALT:-0} ${BENCH_ARGS}"
+B="python bench.py --full --steps ${STEPS:-10} --warmup 2 --no-cpu --no-cstr ${LEGS:---no-ntt --no-c5} --alt-bits ${ALT:-0} ${BENCH_ARGS}"
 for r in $(seq 1 ${ROUNDS:-2}); do
   timeout -k 10 300 $B > $OUT/bench_base_$r.log 2>&1 || { echo "base bench failed"; tail -20 $OUT/bench_base_$r.log; exit 1; }
   for v in $VARS; do

@@ -45,7 +45,7 @@ def test_bench_two_ranks_c5_and_gemv_shards_bit_exact():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env["HECTR_DIST_BACKEND"] = "gloo"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "3", "--steps", "2", "--warmup",
-           "1", "--no-cpu", "--no-cstr", "--no-ntt", "--alt-bits", "0", "--c5-batch", "3", "--gemv-batch", "3",
+           "1", "--full", "--no-cpu", "--no-cstr", "--no-ntt", "--alt-bits", "0", "--c5-batch", "3", "--gemv-batch", "3",
            "--c5-gemv-batch", "2", "--check-shards"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
@@ -62,14 +62,14 @@ def test_bench_two_ranks_c5_and_gemv_shards_bit_exact():
 
 
 def test_bench_two_ranks_default_legs():
-    """The driver's N > 1 command shape with every leg bench.py runs there at
-    its defaults (the 60-bit alternates of the headline, config 5 and the gemv
+    """The driver's N > 1 command shape with every leg bench.py --full runs there
+    at its defaults (the 60-bit alternates of the headline, config 5 and the gemv
     leg included; NTT, CSTR and the CPU baseline are N = 1 only), small
     batches: one JSON line carrying each leg's value and both ranks' times."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env["HECTR_DIST_BACKEND"] = "gloo"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "3", "--steps", "2", "--warmup",
-           "1", "--c5-batch", "2", "--gemv-batch", "3", "--c5-gemv-batch", "2"]
+           "1", "--full", "--c5-batch", "2", "--gemv-batch", "3", "--c5-gemv-batch", "2"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
@@ -93,7 +93,7 @@ def test_bench_eight_ranks_shards_bit_exact():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env["HECTR_DIST_BACKEND"] = "gloo"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--batch", "1", "--steps", "2", "--warmup",
-           "1", "--no-cpu", "--no-cstr", "--no-ntt", "--alt-bits", "0", "--c5-batch", "1", "--gemv-batch", "1",
+           "1", "--full", "--no-cpu", "--no-cstr", "--no-ntt", "--alt-bits", "0", "--c5-batch", "1", "--gemv-batch", "1",
            "--c5-gemv-batch", "1", "--check-shards"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=840, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
