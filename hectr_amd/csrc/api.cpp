@@ -32,6 +32,8 @@ static size_t pool_round(size_t b)
 
 static void flush_ew();
 static void fold_cache_trim();
+static unsigned env_u(const char *name, unsigned dflt);
+void gemv_cache_clear();
 
 void *pool_alloc(size_t bytes)
 {
@@ -118,6 +120,38 @@ static bool gemv_fold_fits(const double *Md, unsigned lvl, const he_evk_t rk[]);
 static bool gemv_win_on(unsigned lvl);
 static const FoldEntry &gemv_fold(const double *Md, unsigned lvl, const he_evk_t rk[]);
 static const FoldEntry &rot_fold(unsigned r, unsigned lvl, const he_evk_t rk[]);
+
+// he_gemv's encoded diagonals, cached by content (the caller recomputes the
+// same gain matrices every control step: reference src/hempc.c:232-238), and
+// the whole matrices already seen (HECTR passes the same two every step): the
+// non-zero diagonals' rotations and cached encodings, so a repeat he_gemv
+// costs one compare of the matrix instead of s diagonal keys.
+// gemv_cache_clear frees every block and bumps gen.  Only gemv_now's encodes
+// clear, after he_gemv ran the queued gemvs; whatever else keeps a pointer
+// into the cache across calls (GemvMat, SgRec) keeps the generation it was
+// built under with it, and is dropped where the two differ.
+struct GemvMat {
+  unsigned s, lvl;
+  uint64_t dgen;
+  std::vector<double> M;
+  std::vector<GemvDiags> dgs;  // evk filled per call from its rk
+  std::vector<unsigned> rot;   // the rotation of each diagonal, in dgs order
+};
+struct DiagCache {
+  std::unordered_map<std::string, uint64_t *> pt;
+  std::vector<void *> blocks;  // what the entries live in (one entry or a batch)
+  size_t bytes = 0;
+  std::vector<GemvMat> mats;
+  uint64_t gen = 1;
+};
+static DiagCache g_dc;
+
+// The cache is cleared when it would grow past this (GPQHE_DIAG_MIB, 2 GiB).
+static size_t diag_cache_cap()
+{
+  static const size_t cap = (size_t)env_u("GPQHE_DIAG_MIB", 2048) << 20;
+  return cap;
+}
 
 // Pinned staging ring for small host->device uploads (encode).
 struct Stage {
@@ -306,7 +340,7 @@ struct SgRec {  // a step's gemv, recorded for the next step's speculation
   std::vector<double> M;
   GemvDiags dg;  // its one launch's diagonals (evk filled)
   const he_evk_t *rk;
-  uint64_t gen;
+  uint64_t gen, dgen;  // g_key_gen and g_dc.gen when dg was filled
 };
 static std::vector<SgRec> g_sg_next;  // this step's gemvs (in g_spec_pats_next order)
 struct SpecGemv {
@@ -343,7 +377,6 @@ extern "C" unsigned gpqhe_spec_gemv_taken(void)
 // C1Prov), and the real program then runs without being waited for.  When the
 // replay is still running at he_dcd on two consecutive steps (the caller
 // outruns the device: the replay only adds work to the step's chain) it stops.
-static unsigned env_u(const char *name, unsigned dflt);
 enum : uint8_t { SR_OUT = 0, SR_Y = 1, SR_ENC = 2 };
 struct SdRole {
   uint8_t kind = 0, idx = 0, poly = 0;
@@ -593,7 +626,6 @@ static EwProg g_pew{};
 
 static void flush_pending();
 static void flush_gemvs();
-static unsigned env_u(const char *name, unsigned dflt);
 static bool g_spec_early = false;  // the next step's speculation rides on this step's gemv / ModDown (spec_attach)
 
 static void flush_ew()
@@ -1057,8 +1089,6 @@ extern "C" void hectx_init(unsigned int logn, MPI q, unsigned int slots, uint64_
   p.seed = 0;
   hectx_init_params(&p);
 }
-
-void gemv_cache_clear();
 
 extern "C" void hectx_exit(void)
 {
@@ -1763,6 +1793,28 @@ static bool spec_modup_launch()
   return true;
 }
 
+// k gemvs, each one launch's worth of diagonals: the inner products of all in
+// one launch, and one ModDown of their accumulators (acc, one after another)
+// into y0 (and y1).
+static void gemv_run_jobs(const GemvJobs &jobs, unsigned k, unsigned lvl, uint64_t *acc, size_t ypstride, uint64_t *y0,
+                          uint64_t *y1)
+{
+  k_gemv_inner_jobs(jobs, k, lvl);
+  k_moddown(y0, ypstride, acc, (size_t)(lvl + G.K) * G.n, 2 * k, lvl, 1, k == 1 ? nullptr : y1);
+  // spec_attach predicts which launches take the attached work; should a
+  // launch's own eligibility test (kernels.hip: gemv_inner's z slice, the
+  // ModDown's dropped limbs) ever disagree, the work runs here in its own
+  // launches, same streams and buffers, so the speculation stays valid
+  if (g_sa.sample) {
+    g_sa.sample = false;
+    k_sample_enc(g_sa.noise, g_sa.stream, g_sa.npoly);
+  }
+  if (g_sa.ntt) {
+    g_sa.ntt = false;
+    k_ntt(g_sa.noise, false);
+  }
+}
+
 // The last step's gemvs on this step's encryptions (SpecGemv), right after
 // their combine: one inner-product launch for both (differences formed in the
 // kernel, the speculated ModUp digits), one ModDown with two outputs, and the
@@ -1780,8 +1832,8 @@ static void spec_gemv_launch(const std::vector<PendEnc> &enc, const std::vector<
   for (unsigned i = 0; i < np; i++) {
     const SgRec &r = recs[i];
     if (r.pat.oa != g_smu.pats[i].oa || r.pat.ob != g_smu.pats[i].ob || r.pat.oa >= enc.size() ||
-        r.pat.ob >= enc.size() || r.gen != g_key_gen || !r.dg.count)
-      return;
+        r.pat.ob >= enc.size() || r.gen != g_key_gen || r.dgen != g_dc.gen || !r.dg.count)
+      return;  // (dgen: the diagonal cache was cleared since, r.dg.pt points into freed blocks)
   }
   const unsigned nm = lvl + G.K, ndig = (lvl + G.alpha - 1) / G.alpha;
   const size_t n = G.n, dstride = (size_t)ndig * nm * n, ypw = (size_t)G.L * n;
@@ -1809,19 +1861,7 @@ static void spec_gemv_launch(const std::vector<PendEnc> &enc, const std::vector<
   // only by that ModUp, after the decode in stream order)
   if (!g_spec_early && spec_attach(true, lvl, std::vector<SpecPat>(g_smu.pats), g_smu.pk1))
     g_spec_early = true;
-  k_gemv_inner_jobs(jobs, np, lvl);
-  if (np == 1)
-    k_moddown(g_sg.Y[0], ypw, acc.p, nm * n, 2, lvl, 1);
-  else
-    k_moddown(g_sg.Y[0], ypw, acc.p, nm * n, 4, lvl, 1, g_sg.Y[1]);
-  if (g_sa.sample) {  // (as flush_gemvs: work a launch did not take runs on its own)
-    g_sa.sample = false;
-    k_sample_enc(g_sa.noise, g_sa.stream, g_sa.npoly);
-  }
-  if (g_sa.ntt) {
-    g_sa.ntt = false;
-    k_ntt(g_sa.noise, false);
-  }
+  gemv_run_jobs(jobs, np, lvl, acc.p, ypw, g_sg.Y[0], g_sg.Y[1]);
   g_sg.np = np;
   g_sg.lvl = lvl;
   g_sg.valid = true;
@@ -2335,15 +2375,27 @@ extern "C" void he_rot(he_ct_t *out, const he_ct_t *in, unsigned int rot, const 
 // ---------------------------------------------------------------------------
 // he_gemv: diagonal method, hoisted ModUp, diagonals encoded at scale q_top
 // over the QP basis, one ModDown-and-rescale by P q_top at the end.
-// Encoded diagonals are cached by content (the caller recomputes the same
-// gain matrices every control step: reference src/hempc.c:232-238).
+// Encoded diagonals are cached by content (DiagCache).
 // ---------------------------------------------------------------------------
-// A he_gemv of SpecGemv pattern i: y <- Y_i as two queued copies.  Returns
-// i, or -1 (the normal path).
-static int spec_gemv_take(he_ct_t *y, const double *Md, const he_ct_t *x, const he_evk_t rk[])
+// y = M x, x at level lvl: y's metadata (x's scale read first: y may be x).
+static void gemv_set_meta(he_ct_t *y, const he_ct_t *x, unsigned lvl)
 {
-  if (!g_sg.valid || x->nlimbs != g_sg.lvl || !g_pgemv.empty() || !defer_ok(0))
-    return -1;
+  const double scale = x->scale;
+  y->nlimbs = lvl - 1;
+  y->scale = scale;
+  y->flags = 0;
+}
+
+static int spec_record_pattern(const C1Prov &c, unsigned lvl);
+
+// A he_gemv of SpecGemv pattern i: y <- Y_i, the result speculated at this
+// step's encryptions, as a swap of blocks or two queued copies, and the
+// pattern recorded for the next step as gemv_queued does (before anything
+// flushes the queued differences it matches).  False: the normal path.
+static bool spec_gemv_take(he_ct_t *y, const double *Md, const he_ct_t *x, const he_evk_t rk[])
+{
+  if (!g_sg.valid || !g_pecd.empty() || !g_penc.empty() || x->nlimbs != g_sg.lvl || !g_pgemv.empty() || !defer_ok(0))
+    return false;
   const unsigned lvl = g_sg.lvl, s = G.slots;
   // x = a - b: the last queued op writing each of its polys is a he_sub
   const uint64_t *lz[4] = {};
@@ -2357,7 +2409,7 @@ static int spec_gemv_take(he_ct_t *y, const double *Md, const he_ct_t *x, const 
         lz[2 * p + 1] = sub ? o.b : nullptr;
       }
   if (!lz[0] || !lz[2])
-    return -1;
+    return false;
   // y must not be an operand of the queued ops (the copies run in the queue's
   // order, and a later op reading y would read the copy)
   const uint64_t *ylo = y->data, *yhi = y->data + 2 * pstride(y);
@@ -2365,7 +2417,7 @@ static int spec_gemv_take(he_ct_t *y, const double *Md, const he_ct_t *x, const 
   for (unsigned j = 0; j < g_pew.count; j++) {
     const EwOp &o = g_pew.op[j];
     if (hits(o.a, o.lvl) || hits(o.b, o.lvl) || hits(o.s, o.lvl))
-      return -1;
+      return false;
   }
   auto fresh = [&](const uint64_t *p, uint64_t stream, bool c0) {
     auto it = g_prov.find(p);
@@ -2381,7 +2433,7 @@ static int spec_gemv_take(he_ct_t *y, const double *Md, const he_ct_t *x, const 
       continue;
     const size_t ypw = (size_t)G.L << G.logn;
     if (!ew_defer(2))
-      return -1;
+      return false;
     g_sg.used[i] = true;
     g_sg_taken++;
     prov_forget(y->data, pstride(y));
@@ -2395,9 +2447,19 @@ static int spec_gemv_take(he_ct_t *y, const double *Md, const he_ct_t *x, const 
       for (unsigned p = 0; p < 2; p++)
         ew_push(EW_COPY, limb(y, p, 0), g_sg.Y[i] + p * ypw, nullptr, nullptr, lvl - 1);
     }
-    return (int)i;
+    auto pv = g_prov.find(limb(x, 1, 0));
+    const int pat =
+        pv != g_prov.end() && pv->second.sub && pv->second.lvl == lvl ? spec_record_pattern(pv->second, lvl) : -1;
+    // Y_i was computed from the cached diagonals in stream order, before any
+    // block a later clear of the cache freed could be written again, so it
+    // is good to take whatever happened to the cache since.  Its record goes
+    // on to the next step only while r.dg still points into the cache.
+    if (pat >= 0 && (size_t)pat == g_sg_next.size() && r.dgen == g_dc.gen)
+      g_sg_next.push_back({g_spec_pats_next[pat], r.M, r.dg, rk, g_key_gen, g_dc.gen});
+    gemv_set_meta(y, x, lvl);
+    return true;
   }
-  return -1;
+  return false;
 }
 
 // The pattern of a gemv input c whose c1 is the difference of two of this
@@ -2423,32 +2485,15 @@ static void spec_record_gemv(int pat, const double *Md, const PendGemv &pg, cons
   if (pat < 0 || pg.dgs.size() != 1 || (size_t)pat != g_sg_next.size())
     return;
   const size_t mwords = 2 * (size_t)G.slots * G.slots;
-  g_sg_next.push_back({g_spec_pats_next[pat], std::vector<double>(Md, Md + mwords), pg.dgs[0], rk, g_key_gen});
+  g_sg_next.push_back(
+      {g_spec_pats_next[pat], std::vector<double>(Md, Md + mwords), pg.dgs[0], rk, g_key_gen, g_dc.gen});
 }
-
-static std::unordered_map<std::string, uint64_t *> g_gemv_cache;
-static std::vector<void *> g_gemv_blocks;  // what the cache's entries live in (one entry or a batch)
-static size_t g_gemv_cache_bytes = 0;
-
-// Whole matrices already seen (HECTR passes the same two gain matrices every
-// step): the non-zero diagonals' rotations and cached encodings, so a repeat
-// he_gemv costs one compare of the matrix instead of s diagonal keys.
-struct GemvMat {
-  unsigned s, lvl;
-  std::vector<double> M;
-  std::vector<GemvDiags> dgs;  // evk filled per call from its rk
-  std::vector<unsigned> rot;   // the rotation of each diagonal, in dgs order
-};
-static std::vector<GemvMat> g_gemv_mats;
 
 void gemv_cache_clear()
 {
-  for (void *b : g_gemv_blocks)
+  for (void *b : g_dc.blocks)
     pool_free(b);
-  g_gemv_blocks.clear();
-  g_gemv_cache.clear();
-  g_gemv_cache_bytes = 0;
-  g_gemv_mats.clear();
+  g_dc = DiagCache{{}, {}, 0, {}, g_dc.gen + 1};  // (what older generations recorded never matches again)
 }
 
 static std::string diag_key(const double *diag, unsigned s, unsigned lvl)
@@ -2458,31 +2503,65 @@ static std::string diag_key(const double *diag, unsigned s, unsigned lvl)
   return key;
 }
 
-// Would encoding one more diagonal at this level overflow the cache (and so
-// clear it)?  he_gemv flushes its pending launch before that happens.
-static bool diag_cache_full(unsigned lvl)
+// Would encoding count more diagonals at this level overflow the cache (and
+// so clear it)?  he_gemv runs what refers to the cache before that happens.
+static bool diag_cache_full(unsigned lvl, unsigned count = 1)
 {
   const size_t bytes = ((size_t)(lvl + G.K) << G.logn) * 8;
-  return g_gemv_cache_bytes + bytes > ((size_t)1 << 31);
+  return g_dc.bytes + count * bytes > diag_cache_cap();
 }
 
 static const uint64_t *diag_pt(const double *diag, unsigned s, unsigned lvl)
 {
   const std::string key = diag_key(diag, s, lvl);
-  auto it = g_gemv_cache.find(key);
-  if (it != g_gemv_cache.end())
+  auto it = g_dc.pt.find(key);
+  if (it != g_dc.pt.end())
     return it->second;
   unsigned mods[GPQHE_MAXMOD];
   const unsigned nm = basis_qp(lvl, mods);
   const size_t bytes = ((size_t)nm << G.logn) * 8;
-  if (g_gemv_cache_bytes + bytes > ((size_t)1 << 31))
+  if (diag_cache_full(lvl))
     gemv_cache_clear();
   uint64_t *p = (uint64_t *)pool_alloc(bytes);
-  g_gemv_blocks.push_back(p);
+  g_dc.blocks.push_back(p);
   encode_limbs(p, diag, s, (double)G.q[lvl - 1], mods, nm);
-  g_gemv_cache[key] = p;
-  g_gemv_cache_bytes += bytes;
+  g_dc.pt[key] = p;
+  g_dc.bytes += bytes;
   return p;
+}
+
+// The non-zero diagonals of M in increasing d: f(d, diag), diag the s complex
+// values of diagonal d (row i's is in column i + d, cyclically).
+template <class F> static void for_each_diagonal(const double *Md, F &&f)
+{
+  const unsigned s = G.slots;
+  std::vector<double> diag(2 * (size_t)s);
+  for (unsigned d = 0; d < s; d++) {
+    bool nz = false;
+    for (unsigned i = 0; i < s; i++) {
+      const size_t src = (size_t)i * s + (i + d) % s;
+      diag[2 * i] = Md[2 * src];
+      diag[2 * i + 1] = Md[2 * src + 1];
+      nz |= diag[2 * i] != 0.0 || diag[2 * i + 1] != 0.0;
+    }
+    if (nz)
+      f(d, diag.data());
+  }
+}
+
+// Diagonal d, encoded at pt, joins the launch being filled; a launch that is
+// full (GemvDiags::MAX) goes to full(dg) and the next one starts.
+template <class F>
+static void diags_append(GemvDiags &dg, unsigned d, const uint64_t *pt, const he_evk_t rk[], F &&full)
+{
+  const uint64_t g = d == 0 ? 1 : galois_of_rot(d);
+  dg.evk[dg.count] = d == 0 ? nullptr : find_rot_key(rk, d, g)->data;
+  dg.pt[dg.count] = pt;
+  dg.g[dg.count] = g;
+  if (++dg.count == GemvDiags::MAX) {
+    full(dg);
+    dg.count = 0;
+  }
 }
 
 // x = a - b, both polys written by queued he_sub ops that nothing else in the
@@ -2585,38 +2664,24 @@ static void flush_gemvs()
         jobs.j[i].y1 = q[i].lb1;
       }
     }
-    k_gemv_inner_jobs(jobs, k, lvl);
-  } else {
-    for (unsigned i = 0; i < k; i++)
-      if (q[i].lb0)
-        flush_ew();  // the queued differences, materialised first
-    for (unsigned i = 0; i < k; i++) {
-      uint64_t *a = acc.p + (size_t)i * 2 * nm * n;
-      bool started = false;
-      for (const GemvDiags &dg : q[i].dgs) {
-        k_gemv_inner(a, Dp[i], q[i].x0, q[i].x1, lvl, dg, started);
-        started = true;
-      }
-      if (!started)  // all-zero matrix
-        HIP_CHECK(hipMemsetAsync(a, 0, 2 * nm * n * 8, G.stream));
+    gemv_run_jobs(jobs, k, lvl, acc.p, q[0].ypstride, q[0].y, q[k - 1].y);
+    return;
+  }
+  for (unsigned i = 0; i < k; i++)
+    if (q[i].lb0)
+      flush_ew();  // the queued differences, materialised first
+  for (unsigned i = 0; i < k; i++) {
+    uint64_t *a = acc.p + (size_t)i * 2 * nm * n;
+    bool started = false;
+    for (const GemvDiags &dg : q[i].dgs) {
+      k_gemv_inner(a, Dp[i], q[i].x0, q[i].x1, lvl, dg, started);
+      started = true;
     }
+    if (!started)  // all-zero matrix
+      HIP_CHECK(hipMemsetAsync(a, 0, 2 * nm * n * 8, G.stream));
   }
-  if (k == 1)
-    k_moddown(q[0].y, q[0].ypstride, acc.p, nm * n, 2, lvl, 1);
-  else
-    k_moddown(q[0].y, q[0].ypstride, acc.p, nm * n, 4, lvl, 1, q[1].y);
-  // spec_attach predicts which launches take the attached work; should a
-  // launch's own eligibility test (kernels.hip: gemv_inner's z slice, the
-  // ModDown's dropped limbs) ever disagree, the work runs here in its own
-  // launches, same streams and buffers, so the speculation stays valid
-  if (g_sa.sample) {
-    g_sa.sample = false;
-    k_sample_enc(g_sa.noise, g_sa.stream, g_sa.npoly);
-  }
-  if (g_sa.ntt) {
-    g_sa.ntt = false;
-    k_ntt(g_sa.noise, false);
-  }
+  // (nothing is attached to these launches: spec_attach runs only above)
+  k_moddown(q[0].y, q[0].ypstride, acc.p, nm * n, 2 * k, lvl, 1, k == 1 ? nullptr : q[1].y);
 }
 
 // Unqueued he_gemv for matrices whose diagonals may overflow the cache: a
@@ -2628,116 +2693,111 @@ static void gemv_now(he_ct_t *y, const double *Md, const he_ct_t *x, const he_ev
   const size_t n = G.n;
   Ws D((size_t)ndig * nm * n), acc(2 * nm * n);
   hoist_modup(D.p, x, lvl);
-  std::vector<double> diag(2 * (size_t)s);
   GemvDiags dg{};
   bool started = false;
-  auto flush = [&]() {
-    if (!dg.count)
-      return;
-    k_gemv_inner(acc.p, D.p, limb(x, 0, 0), limb(x, 1, 0), lvl, dg, started);
+  auto launch = [&](const GemvDiags &l) {
+    k_gemv_inner(acc.p, D.p, limb(x, 0, 0), limb(x, 1, 0), lvl, l, started);
     started = true;
-    dg.count = 0;
   };
-  for (unsigned d = 0; d < s; d++) {
-    bool nz = false;
-    for (unsigned i = 0; i < s; i++) {
-      const size_t src = (size_t)i * s + (i + d) % s;
-      diag[2 * i] = Md[2 * src];
-      diag[2 * i + 1] = Md[2 * src + 1];
-      nz |= diag[2 * i] != 0.0 || diag[2 * i + 1] != 0.0;
+  for_each_diagonal(Md, [&](unsigned d, const double *diag) {
+    if (diag_cache_full(lvl) && dg.count) {  // the cache may be cleared below: launch what refers to it first
+      launch(dg);
+      dg.count = 0;
     }
-    if (!nz)
-      continue;
-    if (diag_cache_full(lvl))
-      flush();  // the cache may be cleared below: launch what refers to it first
-    const uint64_t *pt = diag_pt(diag.data(), s, lvl);
-    const uint64_t g = d == 0 ? 1 : galois_of_rot(d);
-    const he_evk_t *k = d == 0 ? nullptr : find_rot_key(rk, d, g);
-    dg.evk[dg.count] = k ? k->data : nullptr;
-    dg.pt[dg.count] = pt;
-    dg.g[dg.count] = g;
-    if (++dg.count == GemvDiags::MAX)
-      flush();
-  }
-  flush();
+    diags_append(dg, d, diag_pt(diag, s, lvl), rk, launch);
+  });
+  if (dg.count)
+    launch(dg);
   if (!started)  // all-zero matrix
     HIP_CHECK(hipMemsetAsync(acc.p, 0, 2 * nm * n * 8, G.stream));
-  const double scale = x->scale;
   k_moddown(y->data, pstride(y), acc.p, nm * n, 2, lvl, 1);
-  y->nlimbs = lvl - 1;
-  y->scale = scale;
-  y->flags = 0;
+  gemv_set_meta(y, x, lvl);
 }
 
-extern "C" void he_gemv(he_ct_t *y, const gpqhe_complex_t M[], const he_ct_t *x, const he_evk_t rk[])
+// n >= 2^13: the windowed batch path on one ciphertext, unqueued.  It takes
+// no part in the small-N step's queues and speculation (check_ctx drops
+// any pending speculative ModUp): those serve HECTR's own ring (n <= 2^12),
+// where a step is a handful of small launches; at 2^13 and above a gemv is
+// tens of microseconds of device work on its own.  (In place, y == x, is
+// fine: every input word is read before the ModDown writes y.)
+static bool gemv_folded(he_ct_t *y, const double *Md, const he_ct_t *x, const he_evk_t rk[], unsigned lvl, bool lazy)
 {
-  HPROF("gemv");
-  if (!G.init)
-    gpqhe_die("context not initialised (hectx_init)");
-  // x may be a queued difference: left queued when the inner products can
-  // form it (ew_lazy_sub, only with x's ModUp digits precomputed), else run
-  // the result speculated at this step's encryptions (SpecGemv): two queued
-  // copies, and the pattern recorded for the next step as below (before
-  // anything flushes the queued differences it matches)
-  if (g_sg.valid && g_pecd.empty() && g_penc.empty()) {
-    if (const int i = spec_gemv_take(y, (const double *)M, x, rk); i >= 0) {
-      const unsigned lvl = x->nlimbs;
-      auto pv = g_prov.find(limb(x, 1, 0));
-      const int pat =
-          pv != g_prov.end() && pv->second.sub && pv->second.lvl == lvl ? spec_record_pattern(pv->second, lvl) : -1;
-      if (pat >= 0 && (size_t)pat == g_sg_next.size()) {
-        const SgRec &r = g_sg.rec[i];
-        g_sg_next.push_back({g_spec_pats_next[pat], r.M, r.dg, rk, g_key_gen});
-      }
-      y->nlimbs = lvl - 1;
-      y->scale = x->scale;
-      y->flags = 0;
+  if (!gemv_win_on(lvl) || !gemv_fold_fits(Md, lvl, rk))
+    return false;
+  if (lazy)
+    flush_ew();
+  check_ctx();
+  prov_forget(y->data, pstride(y));
+  const FoldEntry &f = gemv_fold(Md, lvl, rk);
+  FoldUse use(f);
+  k_gemv_batch_ex(y->data, 0, pstride(y), x->data, 0, pstride(x), 1, lvl, f.K, f.d.data(), (unsigned)f.d.size(), 1);
+  gemv_set_meta(y, x, lvl);
+  return true;
+}
+
+// A matrix not among g_dc.mats: its non-zero diagonals, their encodings looked
+// up or made, in as few launches as possible (GemvDiags::MAX each, evk from
+// rk), kept for the next he_gemv of the same matrix.
+static const GemvMat &gemv_mat_new(const double *Md, unsigned lvl, const he_evk_t rk[])
+{
+  const unsigned s = G.slots;
+  // diagonals not cached yet (host-FFT sizes) are encoded together after the
+  // walk: one upload and one lift + NTT launch for all of them
+  const bool batch_enc = s < gpu_ecd_min();
+  const size_t n = G.n, per = (size_t)(lvl + G.K) << G.logn;
+  std::vector<std::string> keys;  // of every non-zero diagonal
+  std::vector<size_t> fresh;      // the ones to encode (indices in keys)
+  std::vector<int64_t> newcoef;
+  std::vector<unsigned> rots;
+  for_each_diagonal(Md, [&](unsigned d, const double *diag) {
+    keys.push_back(diag_key(diag, s, lvl));
+    rots.push_back(d);
+    if (g_dc.pt.count(keys.back()))
+      return;
+    if (!batch_enc) {
+      diag_pt(diag, s, lvl);
       return;
     }
+    g_dc.pt[keys.back()] = nullptr;  // (a repeat of this diagonal finds it; set below)
+    newcoef.resize((fresh.size() + 1) * n);
+    hm_encode_coeffs(newcoef.data() + fresh.size() * n, diag, s, n, (double)G.q[lvl - 1]);
+    fresh.push_back(keys.size() - 1);
+  });
+  if (!fresh.empty()) {
+    const unsigned cnt = (unsigned)fresh.size();
+    uint64_t *slab = (uint64_t *)pool_alloc((size_t)cnt * per * 8);
+    g_dc.blocks.push_back(slab);
+    Ws dcoef(newcoef.size());
+    upload(dcoef.p, newcoef.data(), newcoef.size() * 8);
+    unsigned mods[GPQHE_MAXMOD];
+    const unsigned nm = basis_qp(lvl, mods);
+    k_lift_ntt(limbset(slab, mods, nm, cnt, per), (const int64_t *)dcoef.p);
+    for (unsigned i = 0; i < cnt; i++)
+      g_dc.pt[keys[fresh[i]]] = slab + (size_t)i * per;
+    g_dc.bytes += (size_t)cnt * per * 8;
   }
-  const uint64_t *lz[4];
-  const bool lazy = ew_lazy_sub(y, x, lz);
-  if (!lazy)
-    flush_ew();
-  if (!g_pecd.empty() || !g_penc.empty())
-    flush_pending();  // x may be a queued encryption
-  const unsigned lvl = x->nlimbs, s = G.slots;
-  if (lvl < 2)
-    gpqhe_die("he_gemv: input at the lowest level");
-  const double *Md = (const double *)M;
-  // n >= 2^13: the windowed batch path on one ciphertext, unqueued.  It takes
-  // no part in the small-N step's queues and speculation (check_ctx drops
-  // any pending speculative ModUp): those serve HECTR's own ring (n <= 2^12),
-  // where a step is a handful of small launches; at 2^13 and above a gemv is
-  // tens of microseconds of device work on its own.  (In place, y == x, is
-  // fine: every input word is read before the ModDown writes y.)
-  if (gemv_win_on(lvl) && gemv_fold_fits(Md, lvl, rk)) {
-    if (lazy)
-      flush_ew();
-    check_ctx();
-    prov_forget(y->data, pstride(y));
-    const FoldEntry &f = gemv_fold(Md, lvl, rk);
-    FoldUse use(f);
-    const double scale = x->scale;
-    k_gemv_batch_ex(y->data, 0, pstride(y), x->data, 0, pstride(x), 1, lvl, f.K, f.d.data(), (unsigned)f.d.size(), 1);
-    y->nlimbs = lvl - 1;
-    y->scale = scale;
-    y->flags = 0;
-    return;
-  }
-  // queue behind the pending gemv only when the two are independent, at one
-  // level, with one output layout, and no diagonal encode can clear the
-  // cache the pending one refers to
+  GemvMat gm{s, lvl, g_dc.gen, std::vector<double>(Md, Md + 2 * (size_t)s * s), {}, rots};
+  GemvDiags dg{};
+  auto push = [&](const GemvDiags &l) { gm.dgs.push_back(l); };
+  for (size_t r = 0; r < rots.size(); r++)
+    diags_append(dg, rots[r], g_dc.pt[keys[r]], rk, push);
+  if (dg.count)
+    push(dg);
+  if (g_dc.mats.size() >= 8)
+    g_dc.mats.erase(g_dc.mats.begin());
+  g_dc.mats.push_back(std::move(gm));
+  return g_dc.mats.back();
+}
+
+// The queued path: behind the pending gemv when the two are independent, at
+// one level, with one output layout (the caller saw that no diagonal encode
+// can clear the cache the pending one refers to).  lz: x's queued difference
+// (ew_lazy_sub), or null.
+static void gemv_queued(he_ct_t *y, const double *Md, const he_ct_t *x, const he_evk_t rk[], unsigned lvl,
+                        const uint64_t *const *lz)
+{
   static const bool defer = env_u("GPQHE_DEFER", 1) && env_u("GPQHE_DEFER_GEMV", 1);
-  const size_t dbytes = ((size_t)(lvl + G.K) << G.logn) * 8;
-  const bool may_clear = g_gemv_cache_bytes + (size_t)s * dbytes > ((size_t)1 << 31);
-  if (may_clear) {
-    // the diagonal cache may be cleared inside this call: unqueued form
-    flush_gemvs();
-    flush_ew();
-    gemv_now(y, Md, x, rk, lvl);
-    return;
-  }
+  const unsigned s = G.slots;
   if (!g_pgemv.empty()) {
     const PendGemv &p = g_pgemv.back();
     if (g_pgemv.size() >= 2 || p.lvl != lvl || p.ypstride != pstride(y) || x->data == (void *)p.y ||
@@ -2762,117 +2822,65 @@ extern "C" void he_gemv(he_ct_t *y, const gpqhe_complex_t M[], const he_ct_t *x,
         }
     pat = spec_record_pattern(c, lvl);
   }
-  if (lazy && pg.dspec) {
+  if (lz && pg.dspec) {
     pg.la0 = lz[0];
     pg.lb0 = lz[1];
     pg.la1 = lz[2];
     pg.lb1 = lz[3];
-  } else if (lazy) {
+  } else if (lz) {
     flush_ew();  // the ModUp reads x1 itself
   }
-  const size_t mwords = 2 * (size_t)s * s;
-  for (const GemvMat &gm : g_gemv_mats)
-    if (gm.s == s && gm.lvl == lvl && !memcmp(gm.M.data(), Md, mwords * 8)) {
-      size_t r = 0;
-      pg.dgs = gm.dgs;
-      for (GemvDiags &dg : pg.dgs)
-        for (unsigned e = 0; e < dg.count; e++, r++)
-          dg.evk[e] = gm.rot[r] ? find_rot_key(rk, gm.rot[r], dg.g[e])->data : nullptr;
-      spec_record_gemv(pat, Md, pg, rk);
-      g_pgemv.push_back(std::move(pg));
-      if (!defer)
-        flush_gemvs();
-      y->nlimbs = lvl - 1;
-      y->scale = x->scale;
-      y->flags = 0;
-      return;
+  const GemvMat *gm = nullptr;
+  for (const GemvMat &m : g_dc.mats)
+    if (m.s == s && m.lvl == lvl && m.dgen == g_dc.gen && !memcmp(m.M.data(), Md, m.M.size() * 8)) {
+      gm = &m;
+      break;
     }
-  std::vector<unsigned> rots;
-  std::vector<double> diag(2 * (size_t)s);
-  // diagonals not cached yet (host-FFT sizes) are encoded together after the
-  // loop: one upload and one lift + NTT launch for all of them
-  const bool batch_enc = s < gpu_ecd_min();
-  const size_t n = G.n, per = (size_t)(lvl + G.K) << G.logn;
-  std::vector<std::string> newkeys;
-  std::unordered_map<std::string, unsigned> newidx;
-  std::vector<int64_t> newcoef;
-  struct Fix {
-    size_t launch;
-    unsigned e, idx;
-  };
-  std::vector<Fix> fixes;
-  // all non-zero diagonals in as few launches as possible (GemvDiags::MAX each)
-  GemvDiags dg{};
-  for (unsigned d = 0; d < s; d++) {
-    bool nz = false;
-    for (unsigned i = 0; i < s; i++) {
-      const size_t src = (size_t)i * s + (i + d) % s;
-      diag[2 * i] = Md[2 * src];
-      diag[2 * i + 1] = Md[2 * src + 1];
-      nz |= diag[2 * i] != 0.0 || diag[2 * i + 1] != 0.0;
-    }
-    if (!nz)
-      continue;
-    const uint64_t *pt = nullptr;
-    std::string key = diag_key(diag.data(), s, lvl);
-    auto it = g_gemv_cache.find(key);
-    if (it != g_gemv_cache.end()) {
-      pt = it->second;
-    } else if (!batch_enc) {
-      pt = diag_pt(diag.data(), s, lvl);
-    } else {
-      auto jt = newidx.find(key);
-      unsigned idx;
-      if (jt == newidx.end()) {
-        idx = (unsigned)newkeys.size();
-        newidx.emplace(key, idx);
-        newkeys.push_back(std::move(key));
-        newcoef.resize((size_t)(idx + 1) * n);
-        hm_encode_coeffs(newcoef.data() + (size_t)idx * n, diag.data(), s, n, (double)G.q[lvl - 1]);
-      } else {
-        idx = jt->second;
-      }
-      fixes.push_back({pg.dgs.size(), dg.count, idx});
-    }
-    const uint64_t g = d == 0 ? 1 : galois_of_rot(d);
-    const he_evk_t *k = d == 0 ? nullptr : find_rot_key(rk, d, g);
-    dg.evk[dg.count] = k ? k->data : nullptr;
-    dg.pt[dg.count] = pt;
-    dg.g[dg.count] = g;
-    rots.push_back(d);
-    if (++dg.count == GemvDiags::MAX) {
-      pg.dgs.push_back(dg);
-      dg.count = 0;
-    }
+  if (gm) {
+    size_t r = 0;
+    pg.dgs = gm->dgs;
+    for (GemvDiags &dg : pg.dgs)
+      for (unsigned e = 0; e < dg.count; e++, r++)
+        dg.evk[e] = gm->rot[r] ? find_rot_key(rk, gm->rot[r], dg.g[e])->data : nullptr;
+  } else {
+    pg.dgs = gemv_mat_new(Md, lvl, rk).dgs;
   }
-  if (dg.count)
-    pg.dgs.push_back(dg);
-  if (!newkeys.empty()) {
-    const unsigned cnt = (unsigned)newkeys.size();
-    uint64_t *slab = (uint64_t *)pool_alloc((size_t)cnt * per * 8);
-    g_gemv_blocks.push_back(slab);
-    Ws dcoef(newcoef.size());
-    upload(dcoef.p, newcoef.data(), newcoef.size() * 8);
-    unsigned mods[GPQHE_MAXMOD];
-    const unsigned nm = basis_qp(lvl, mods);
-    k_lift_ntt(limbset(slab, mods, nm, cnt, per), (const int64_t *)dcoef.p);
-    for (unsigned i = 0; i < cnt; i++)
-      g_gemv_cache[newkeys[i]] = slab + (size_t)i * per;
-    g_gemv_cache_bytes += (size_t)cnt * per * 8;
-    for (const Fix &f : fixes)
-      pg.dgs[f.launch].pt[f.e] = slab + (size_t)f.idx * per;
-  }
-  if (g_gemv_mats.size() >= 8)
-    g_gemv_mats.erase(g_gemv_mats.begin());
-  g_gemv_mats.push_back({s, lvl, std::vector<double>(Md, Md + mwords), pg.dgs, rots});
-  const double scale = x->scale;
   spec_record_gemv(pat, Md, pg, rk);
   g_pgemv.push_back(std::move(pg));
   if (!defer)
     flush_gemvs();
-  y->nlimbs = lvl - 1;
-  y->scale = scale;
-  y->flags = 0;
+  gemv_set_meta(y, x, lvl);
+}
+
+extern "C" void he_gemv(he_ct_t *y, const gpqhe_complex_t M[], const he_ct_t *x, const he_evk_t rk[])
+{
+  HPROF("gemv");
+  if (!G.init)
+    gpqhe_die("context not initialised (hectx_init)");
+  const double *Md = (const double *)M;
+  if (spec_gemv_take(y, Md, x, rk))
+    return;
+  // x may be a queued difference: left queued when the inner products can
+  // form it (ew_lazy_sub, only with x's ModUp digits precomputed), else run now
+  const uint64_t *lz[4];
+  const bool lazy = ew_lazy_sub(y, x, lz);
+  if (!lazy)
+    flush_ew();
+  if (!g_pecd.empty() || !g_penc.empty())
+    flush_pending();  // x may be a queued encryption
+  const unsigned lvl = x->nlimbs;
+  if (lvl < 2)
+    gpqhe_die("he_gemv: input at the lowest level");
+  if (gemv_folded(y, Md, x, rk, lvl, lazy))
+    return;
+  if (diag_cache_full(lvl, G.slots)) {
+    // the diagonal cache may be cleared inside this call: unqueued form
+    flush_gemvs();
+    flush_ew();
+    gemv_now(y, Md, x, rk, lvl);
+    return;
+  }
+  gemv_queued(y, Md, x, rk, lvl, lazy ? lz : nullptr);
 }
 
 // ===========================================================================
@@ -3033,31 +3041,6 @@ static bool gemv_win_on(unsigned lvl)
   return on && k_gemv_win_ok(lvl);
 }
 
-// The rotations of M's non-zero diagonals, and (diags) the diagonals
-// themselves, slots complex values each.
-static std::vector<unsigned> gemv_diagonals(const double *Md, std::vector<double> *diags)
-{
-  const unsigned s = G.slots;
-  std::vector<unsigned> ds;
-  for (unsigned d = 0; d < s; d++) {
-    bool nz = false;
-    for (unsigned i = 0; i < s && !nz; i++) {
-      const size_t src = (size_t)i * s + (i + d) % s;
-      nz = Md[2 * src] != 0.0 || Md[2 * src + 1] != 0.0;
-    }
-    if (!nz)
-      continue;
-    ds.push_back(d);
-    if (diags)
-      for (unsigned i = 0; i < s; i++) {
-        const size_t src = (size_t)i * s + (i + d) % s;
-        diags->push_back(Md[2 * src]);
-        diags->push_back(Md[2 * src + 1]);
-      }
-  }
-  return ds;
-}
-
 static const FoldEntry *fold_find(const double *Md, unsigned lvl, const he_evk_t rk[])
 {
   const unsigned s = G.slots;
@@ -3075,7 +3058,8 @@ static bool gemv_fold_fits(const double *Md, unsigned lvl, const he_evk_t rk[])
 {
   if (fold_find(Md, lvl, rk))
     return true;
-  const size_t E = gemv_diagonals(Md, nullptr).size();
+  size_t E = 0;
+  for_each_diagonal(Md, [&](unsigned, const double *) { E++; });
   const size_t pts = E * (((size_t)lvl + G.K) << G.logn) * 8;
   return k_gemv_fold_words((unsigned)E, lvl) * 8 + pts <= fold_cap();
 }
@@ -3089,7 +3073,11 @@ static const FoldEntry &gemv_fold(const double *Md, unsigned lvl, const he_evk_t
   const unsigned s = G.slots;
   const size_t mwords = 2 * (size_t)s * s;
   std::vector<double> diags;
-  const std::vector<unsigned> ds = gemv_diagonals(Md, &diags);
+  std::vector<unsigned> ds;
+  for_each_diagonal(Md, [&](unsigned d, const double *diag) {
+    ds.push_back(d);
+    diags.insert(diags.end(), diag, diag + 2 * (size_t)s);
+  });
   const unsigned E = (unsigned)ds.size();
   unsigned mods[GPQHE_MAXMOD];
   const unsigned nm = basis_qp(lvl, mods);

@@ -10,6 +10,11 @@ state (src/ctr.c:461-480), he_sub x2, he_gemv x2, he_add / he_neg
 import numpy as np
 
 PARAMS_REF = dict(logn=12, logq=109, slots=16, log_delta=50)  # src/ctr.c:514-518
+# he_gemv calls an "evict" step of speculative_gemvs adds.  Under a 5 MiB
+# diagonal cache: the first is queued (cache at 4.5 MiB), the second runs
+# unqueued and clears the cache at its sixth diagonal, the third and fourth are
+# queued into freed 1.5 MiB blocks, the fifth runs unqueued again.
+EVICT_EXTRAS = 5
 
 
 def keys(e, rot=True):
@@ -152,14 +157,20 @@ def rekeyed_steps(e, seed=1234, rng_seed=41):
     return res
 
 
-def speculative_gemvs(e, seed=1234, rng_seed=53, plan=None):
+def speculative_gemvs(e, seed=1234, rng_seed=53, plan=None, taken=None):
     """HECTR's step with its own call order (all five encodes, all five
     encryptions, the plaintexts freed: src/ctr.c:461-480, which starts the
     early combine and, from the third step on, the speculated gemvs of the
     last step's pattern, api.cpp SpecGemv), and steps where the speculation
     must not be taken: a gemv matrix that changed, the subtraction's operands
     swapped, an encryption overwritten before its he_sub, the gemvs in the
-    other order, the rotation keys regenerated in place, and one gemv only."""
+    other order, the rotation keys regenerated in place, and one gemv only.
+    "evict" / "evict_ct": the normal step, then in the same step EVICT_EXTRAS
+    more he_gemv calls with fresh dense matrices, on ud / on an encryption (which
+    records no speculation pattern), into ciphertexts exported at the end:
+    with a small diagonal cache (GPQHE_DIAG_MIB) they clear it and take the
+    freed blocks while the next step's speculation records point there.
+    taken: a list that gets gpqhe_spec_gemv_taken() after every step."""
     e.init(**PARAMS_REF)
     e.set_seed(seed)
     rng = np.random.default_rng(rng_seed)
@@ -214,6 +225,11 @@ def speculative_gemvs(e, seed=1234, rng_seed=53, plan=None):
         else:
             e.gemv(ya, Ma.ravel(), xd, rk)
             e.gemv(yb, M2.ravel(), ud, rk)
+        if kind in ("evict", "evict_ct"):
+            for _ in range(EVICT_EXTRAS):
+                Me = (rng.uniform(-1, 1, (s, s)) + 0j).astype(np.complex128)
+                keep.append(e.ct())
+                e.gemv(keep[-1], Me.ravel(), ud if kind == "evict" else cts[0], rk)
         e.add(du, ya, yb)
         e.neg(du)
         e.add(du, du, cts[0])
@@ -225,6 +241,8 @@ def speculative_gemvs(e, seed=1234, rng_seed=53, plan=None):
         res.append(e.decrypt(du, sk))
         for x in cts:
             e.free(x)
+        if taken is not None and hasattr(e.lib, "gpqhe_spec_gemv_taken"):
+            taken.append(int(e.lib.gpqhe_spec_gemv_taken()))
     res += [e.export(x) for x in keep]
     return res
 
@@ -238,3 +256,18 @@ def mismatches(a, b):
     if len(a) != len(b):
         return [-1]
     return [i for i, (x, y) in enumerate(zip(a, b)) if not np.array_equal(x, y)]
+
+
+def cache_evictions(ora, prod):
+    """speculative_gemvs with the diagonal cache cleared in the fifth step
+    (run with GPQHE_DIAG_MIB=5: a dense 16-slot matrix's diagonals are
+    1.5 MiB at PARAMS_REF), once per evict kind: the objects differing from
+    the oracle's, and the product's speculated-gemv count after every step."""
+    out = {}
+    for kind in ("evict", "evict_ct"):
+        plan = ["same"] * 4 + [kind] + ["same"] * 6
+        taken = []
+        want = speculative_gemvs(ora, plan=plan)
+        got = speculative_gemvs(prod, plan=plan, taken=taken)
+        out[kind] = {"diff": mismatches(want, got), "taken": taken}
+    return out

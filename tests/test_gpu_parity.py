@@ -708,6 +708,46 @@ def test_small_n_switch_off_paths(switch):
     assert res == {k: [] for k in res} and len(res) == 4, res
 
 
+def test_diag_cache_clear():
+    """A clear of he_gemv's diagonal cache (api.cpp DiagCache) between two
+    speculated steps.  The cap is read once per process, so a child runs with
+    GPQHE_DIAG_MIB=5 at HECTR's ring, where a dense 16-slot matrix's diagonals
+    are 1.5 MiB (tests/small_n_steps.py cache_evictions): four steps, a step
+    whose two gemvs are served from the speculation and which then runs five
+    more he_gemv calls with fresh matrices (the second, unqueued, clears the
+    cache; the next two are encoded into blocks it freed: the pool hands out
+    the last freed block of a size first; the fifth, unqueued again, leaves
+    no gemv queued at the step's end), six more steps.  The records the takes
+    carried over point into freed blocks: the next step must run without
+    speculated gemvs.  Extra gemvs on ud ("evict") add speculation records of
+    their own, on an encryption ("evict_ct") none.  Every decoded value and
+    exported object bit-exact vs the oracle; the speculated-gemv count rises
+    before the clear and again after it, and not in the step right after.
+    (Measured: after every step 0 2 4 6 8 8 10 12 14 16 18 for both kinds --
+    and the same with the generation checks taken out of api.cpp: a step with
+    an unqueued he_gemv, the only path that clears the cache, is followed by
+    an unspeculated step in any case, so the test pins the behaviour and does
+    not by itself prove the checks.)"""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, GPQHE_DIAG_MIB="5")
+    r = subprocess.run([sys.executable, os.path.join(root, "tests", "switch_worker.py"), "cache_evictions"], env=env,
+                       cwd=root, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    res = json.loads(r.stdout.strip().splitlines()[-1])
+    print(res)
+    assert sorted(res) == ["evict", "evict_ct"], res
+    for kind, got in res.items():
+        t = got["taken"]  # after each of the 11 steps; the clear is in step 5 (t[4])
+        assert got["diff"] == [], (kind, got)
+        assert len(t) == 11 and t[3] > 0 and t[4] == t[3] + 2, (kind, t)
+        assert t[5] == t[4], (kind, t)
+        assert t[10] > t[4], (kind, t)
+
+
 @pytest.mark.parametrize("name", ["ref", "c1"])
 def test_plaintext_ops_rot0_and_queue_overflow(oracle, product, name):
     """he_add_pt (out != a: a queued copy the add then reads; and in place),
