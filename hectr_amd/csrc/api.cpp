@@ -3,6 +3,7 @@
 // HIP stream; every object payload lives in HBM.  Call-site contract:
 // reference src/ctr.c:445-618 and src/hempc.c:216-274 (see gpqhe.h).
 #include "gpqhe_internal.h"
+#include "../../include/gpqhe_ext.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -34,6 +35,7 @@ static void flush_ew();
 static void fold_cache_trim();
 static unsigned env_u(const char *name, unsigned dflt);
 void gemv_cache_clear();
+static void bsgs_cache_clear();
 
 void *pool_alloc(size_t bytes)
 {
@@ -1123,6 +1125,7 @@ extern "C" void hectx_exit(void)
   g_sd_off = false;
   k_prof_release();
   gemv_cache_clear();
+  bsgs_cache_clear();
   fold_cache_clear();
   g_key_gen++;
   tables_free();
@@ -2881,6 +2884,282 @@ extern "C" void he_gemv(he_ct_t *y, const gpqhe_complex_t M[], const he_ct_t *x,
     return;
   }
   gemv_queued(y, Md, x, rk, lvl, lazy ? lz : nullptr);
+}
+
+// ===========================================================================
+// he_gemv_bsgs (include/gpqhe_ext.h): the baby-step giant-step form of the
+// diagonal method.  With g baby steps and G = ceil(s / g) giant steps,
+//   b_i   = rot(x, i)                                  (hoisted: one ModUp)
+//   u_j   = sum_i P_j,i b_i,  P_j,i = ecd(roll(diag_{jg+i}, jg)) over the q limbs
+//   y     = rescale(sum_j rot(u_j, jg))
+// every step the exact arithmetic of he_rot / he_mul_pt / he_add / he_rescale,
+// so the residues are those of that composition.  Kernels: bsgs.hip.
+// Non-queued: it takes no part in the small-N step's queues and speculation,
+// and he_gemv takes none of this code.
+//
+// The encoded diagonals live in a cache of their own (g_bsgs), keyed by the
+// bytes of M, the level and g, least recently used first out, bounded by
+// diag_cache_cap().  An entry owns its device blocks; nothing outside this
+// section keeps a pointer into one across calls, and a call holds its entry
+// only until it returns (nothing inside a call evicts).
+// ===========================================================================
+struct BsgsPlan {
+  std::vector<double> M;        // the matrix it was made from (compared in place on a lookup)
+  unsigned s = 0, lvl = 0, g = 0;
+  std::vector<unsigned> ds;     // the non-zero diagonals, ascending: pts order
+  std::vector<unsigned> baby;   // the baby rotations they use, ascending: slot order of B
+  std::vector<unsigned> giant;  // the giant steps they use, ascending: row order of tab and U
+  std::vector<int> tab;         // [giant][baby] -> index into pts, -1: none
+  uint64_t *pts = nullptr;      // [ds.size()][lvl][n]
+  int *tab_dev = nullptr;
+  size_t bytes = 0;
+};
+static std::list<BsgsPlan> g_bsgs;
+static size_t g_bsgs_bytes = 0;
+
+static void bsgs_cache_clear()
+{
+  for (BsgsPlan &p : g_bsgs) {
+    pool_free(p.pts);
+    pool_free(p.tab_dev);
+  }
+  g_bsgs.clear();
+  g_bsgs_bytes = 0;
+}
+
+static unsigned bsgs_default_g()
+{
+  unsigned lg = 0;
+  while ((1u << lg) < G.slots)
+    lg++;
+  return 1u << ((lg + 1) / 2);
+}
+
+// Which diagonals, baby rotations and giant steps M uses (host only).
+static void bsgs_plan(BsgsPlan &p, const double *Md, unsigned g)
+{
+  const unsigned s = G.slots, ng = (s + g - 1) / g;
+  std::vector<char> ub(g, 0), uj(ng, 0);
+  for_each_diagonal(Md, [&](unsigned d, const double *) {
+    p.ds.push_back(d);
+    ub[d % g] = 1;
+    uj[d / g] = 1;
+  });
+  std::vector<int> bslot(g, -1), jrow(ng, -1);
+  for (unsigned i = 0; i < g; i++)
+    if (ub[i]) {
+      bslot[i] = (int)p.baby.size();
+      p.baby.push_back(i);
+    }
+  for (unsigned j = 0; j < ng; j++)
+    if (uj[j]) {
+      jrow[j] = (int)p.giant.size();
+      p.giant.push_back(j);
+    }
+  p.tab.assign(p.giant.size() * p.baby.size(), -1);
+  for (size_t e = 0; e < p.ds.size(); e++)
+    p.tab[(size_t)jrow[p.ds[e] / g] * p.baby.size() + bslot[p.ds[e] % g]] = (int)e;
+}
+
+// pts <- P_j,i of every non-zero diagonal d = j g + i, in p.ds order.
+static void bsgs_encode(const BsgsPlan &p, const double *Md, unsigned lvl, unsigned g, uint64_t *pts)
+{
+  const unsigned s = G.slots;
+  unsigned mods[GPQHE_MAXMOD];
+  for (unsigned l = 0; l < lvl; l++)
+    mods[l] = l;
+  std::vector<double> v(2 * (size_t)s);
+  for (size_t e = 0; e < p.ds.size(); e++) {
+    const unsigned d = p.ds[e], sh = d / g * g;
+    for (unsigned k = 0; k < s; k++) {  // roll(diag_d, j g)[k] = diag_d[k - j g]
+      const unsigned i = (k + s - sh) % s;
+      const size_t src = (size_t)i * s + (i + d) % s;
+      v[2 * k] = Md[2 * src];
+      v[2 * k + 1] = Md[2 * src + 1];
+    }
+    encode_limbs(pts + e * ((size_t)lvl << G.logn), v.data(), s, (double)G.q[lvl - 1], mods, lvl);
+  }
+}
+
+static void bsgs_ks_launch(const std::vector<BsgsKsJob> &jobs, unsigned lvl, bool shared_d)
+{
+  const unsigned nm = lvl + G.K, ndig = (lvl + G.alpha - 1) / G.alpha;
+  const size_t bytes = jobs.size() * sizeof(BsgsKsJob);
+  Ws jd((bytes + 7) / 8);
+  upload(jd.p, jobs.data(), bytes);
+  // per job: the key, c0, both accumulators; the digits once per job or per launch
+  const double cnt = (double)jobs.size();
+  k_bsgs_ks((const BsgsKsJob *)jd.p, (unsigned)jobs.size(), lvl,
+            8.0 * G.n * (cnt * (2.0 * ndig * nm + lvl + 2.0 * nm) + (shared_d ? 1.0 : cnt) * ndig * nm));
+}
+
+extern "C" unsigned int he_gemv_bsgs_default_g(void)
+{
+  if (!G.init)
+    gpqhe_die("context not initialised (hectx_init)");
+  return bsgs_default_g();
+}
+
+extern "C" void he_genrk_bsgs(he_evk_t rk[], const poly_mpi_t *sk, unsigned int g)
+{
+  check_ctx();
+  const unsigned s = G.slots;
+  if (!g)
+    g = bsgs_default_g();
+  if (g > s)
+    gpqhe_die("he_genrk_bsgs: g = %u > slots = %u", g, s);
+  if (rk[0].data)
+    obj_free(&rk[0]);
+  rk[0].galois = 1;
+  for (unsigned r = 1; r < s; r++) {
+    if (r < g || r % g == 0)
+      gen_rot_key(&rk[r], galois_of_rot(r), sk);
+    else if (rk[r].data)
+      he_free_evk(&rk[r]);
+  }
+}
+
+extern "C" void he_gemv_bsgs(he_ct_t *y, const gpqhe_complex_t M[], const he_ct_t *x, const he_evk_t rk[],
+                             unsigned int g)
+{
+  HPROF("gemv_bsgs");
+  check_ctx();  // x may be a queued difference or encryption
+  const unsigned s = G.slots, lvl = x->nlimbs;
+  if (!g)
+    g = bsgs_default_g();
+  if (g > s)
+    gpqhe_die("he_gemv_bsgs: g = %u > slots = %u", g, s);
+  if (lvl < 2)
+    gpqhe_die("he_gemv_bsgs: input at the lowest level");
+  const double *Md = (const double *)M;
+  const unsigned nm = lvl + G.K, ndig = (lvl + G.alpha - 1) / G.alpha;
+  const size_t n = G.n, pw = (size_t)lvl * n, accw = 2 * (size_t)nm * n, dw = (size_t)ndig * nm * n;
+  const size_t budget = ((size_t)env_u("GPQHE_WS_MIB", 8192) << 20) / 8;  // words per key-switch workspace
+
+  // the encoded diagonals: cached, or (a set larger than the cache) in workspace
+  const BsgsPlan *plan = nullptr;
+  BsgsPlan tmp;
+  std::unique_ptr<Ws> tmp_pts, tmp_tab;
+  {
+    const size_t mwords = 2 * (size_t)s * s;
+    for (auto it = g_bsgs.begin(); it != g_bsgs.end(); ++it)
+      if (it->s == s && it->lvl == lvl && it->g == g && !memcmp(it->M.data(), Md, mwords * 8)) {
+        g_bsgs.splice(g_bsgs.begin(), g_bsgs, it);
+        plan = &g_bsgs.front();
+        break;
+      }
+    if (!plan) {
+      bsgs_plan(tmp, Md, g);
+      const size_t tabw = (tmp.tab.size() * sizeof(int) + 7) / 8;
+      tmp.bytes = tmp.ds.size() * pw * 8;
+      if (tmp.bytes > diag_cache_cap()) {
+        tmp_pts.reset(new Ws(tmp.ds.size() * pw));
+        tmp_tab.reset(new Ws(tabw));
+        tmp.pts = tmp_pts->p;
+        tmp.tab_dev = (int *)tmp_tab->p;
+      } else if (!tmp.ds.empty()) {
+        while (!g_bsgs.empty() && g_bsgs_bytes + tmp.bytes > diag_cache_cap()) {
+          pool_free(g_bsgs.back().pts);
+          pool_free(g_bsgs.back().tab_dev);
+          g_bsgs_bytes -= g_bsgs.back().bytes;
+          g_bsgs.pop_back();
+        }
+        tmp.pts = (uint64_t *)pool_alloc(tmp.bytes);
+        tmp.tab_dev = (int *)pool_alloc(tabw * 8);
+      }
+      if (!tmp.ds.empty()) {
+        bsgs_encode(tmp, Md, lvl, g, tmp.pts);
+        upload(tmp.tab_dev, tmp.tab.data(), tmp.tab.size() * sizeof(int));
+      }
+      if (tmp_pts || tmp.ds.empty()) {
+        plan = &tmp;
+      } else {
+        tmp.M.assign(Md, Md + mwords);  // the owned copy: made on a miss only
+        tmp.s = s;
+        tmp.lvl = lvl;
+        tmp.g = g;
+        g_bsgs_bytes += tmp.bytes;
+        g_bsgs.push_front(std::move(tmp));
+        plan = &g_bsgs.front();
+      }
+    }
+  }
+  prov_forget(y->data, pstride(y));
+  if (plan->ds.empty()) {  // all-zero matrix
+    for (unsigned p = 0; p < 2; p++)
+      HIP_CHECK(hipMemsetAsync(limb(y, p, 0), 0, (size_t)(lvl - 1) * n * 8, G.stream));
+    gemv_set_meta(y, x, lvl);
+    return;
+  }
+  const unsigned nbs = (unsigned)plan->baby.size(), nj = (unsigned)plan->giant.size();
+  const unsigned has0 = plan->baby[0] == 0, nbr = nbs - has0;
+  const unsigned hasj0 = plan->giant[0] == 0, njr = nj - hasj0;
+  // every key this call reads, before anything is launched
+  std::vector<const he_evk_t *> bkey(nbr), gkey(njr);
+  std::vector<uint64_t> bgal(nbr), ggal(njr);
+  for (unsigned r = 0; r < nbr; r++) {
+    bgal[r] = galois_of_rot(plan->baby[has0 + r]);
+    bkey[r] = find_rot_key(rk, plan->baby[has0 + r], bgal[r]);
+  }
+  for (unsigned r = 0; r < njr; r++) {
+    ggal[r] = galois_of_rot(plan->giant[hasj0 + r] * g);
+    gkey[r] = find_rot_key(rk, plan->giant[hasj0 + r] * g, ggal[r]);
+  }
+
+  // baby steps: B [nbs][2][lvl][n], slot 0 x itself where diagonals use it
+  Ws B((size_t)nbs * 2 * pw);
+  if (has0)
+    for (unsigned p = 0; p < 2; p++)
+      HIP_CHECK(hipMemcpyAsync(B.p + p * pw, limb(x, p, 0), pw * 8, hipMemcpyDeviceToDevice, G.stream));
+  if (nbr) {
+    const unsigned cb = (unsigned)std::min<size_t>(nbr, std::max<size_t>(1, budget / accw));
+    Ws D(dw), acc((size_t)cb * accw);
+    hoist_modup(D.p, x, lvl);
+    for (unsigned r0 = 0; r0 < nbr; r0 += cb) {
+      const unsigned cnt = std::min(cb, nbr - r0);
+      std::vector<BsgsKsJob> jobs(cnt);
+      for (unsigned t = 0; t < cnt; t++)
+        jobs[t] = BsgsKsJob{D.p, limb(x, 0, 0), bkey[r0 + t]->data, acc.p + t * accw, bgal[r0 + t]};
+      bsgs_ks_launch(jobs, lvl, true);
+      k_moddown(B.p + (size_t)(has0 + r0) * 2 * pw, pw, acc.p, (size_t)nm * n, 2 * cnt, lvl, 0);
+    }
+  }
+
+  // the plaintext inner sums: U [nj][2][lvl][n]
+  Ws U((size_t)nj * 2 * pw);
+  k_bsgs_inner(U.p, B.p, plan->pts, plan->tab_dev, nj, nbs, (unsigned)plan->ds.size(), lvl);
+
+  // giant steps: each u_j (j >= 1) rotated by j g through its own ModDown,
+  // then summed (with u_0) over the q limbs; chunks of cg giant steps
+  uint64_t *S = U.p;
+  Ws Sw(njr ? 2 * pw : 0);
+  if (njr) {
+    const unsigned cg = (unsigned)std::min<size_t>(njr, std::max<size_t>(1, budget / (dw + accw + 2 * pw)));
+    Ws Dg((size_t)cg * dw), acc((size_t)cg * accw), R((size_t)cg * 2 * pw);
+    const uint64_t *base = hasj0 ? U.p : nullptr;
+    for (unsigned r0 = 0; r0 < njr; r0 += cg) {
+      const unsigned cnt = std::min(cg, njr - r0);
+      const uint64_t *u = U.p + (size_t)(hasj0 + r0) * 2 * pw;
+      for (unsigned b0 = 0; b0 < cnt; b0 += XPtrs::MAX) {
+        const unsigned c = std::min(XPtrs::MAX, cnt - b0);
+        XPtrs x1{};
+        for (unsigned t = 0; t < c; t++)
+          x1.p[t] = u + (size_t)(b0 + t) * 2 * pw + pw;
+        k_modup_ntt(Dg.p + b0 * dw, x1, c, dw, lvl);
+      }
+      std::vector<BsgsKsJob> jobs(cnt);
+      for (unsigned t = 0; t < cnt; t++)
+        jobs[t] = BsgsKsJob{Dg.p + t * dw, u + (size_t)t * 2 * pw, gkey[r0 + t]->data, acc.p + t * accw, ggal[r0 + t]};
+      bsgs_ks_launch(jobs, lvl, false);
+      k_moddown(R.p, pw, acc.p, (size_t)nm * n, 2 * cnt, lvl, 0);
+      k_bsgs_sum(Sw.p, base, R.p, cnt, 2 * pw, lvl);
+      base = Sw.p;
+    }
+    S = Sw.p;
+  }
+  // rescale by q_top into y (every read of x is already on the stream: y may be x)
+  k_moddown(y->data, pstride(y), S, pw, 2, lvl, 2);
+  gemv_set_meta(y, x, lvl);
 }
 
 // ===========================================================================

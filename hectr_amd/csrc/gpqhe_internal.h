@@ -475,7 +475,8 @@ enum KClass {
   KC_NTT_WHOLE_FWD, KC_NTT_WHOLE_INV, KC_MODUP, KC_KS_INNER, KC_TENSOR, KC_DOWN_CONV, KC_DOWN_COMBINE, KC_KS_COLS,
   KC_KS_ROWS, KC_DN_COLS, KC_DN_ROWS, KC_D2_ROWS, KC_NTT2_COLS_FWD, KC_NTT3_ROWS_FWD, KC_NTT3_ROWS_INV,
   KC_NTT2_COLS_INV, KC_KS_COLS4, KC_NTT_SMALL_FWD, KC_NTT_SMALL_INV, KC_GEMV_INNER, KC_KSQ_DROP, KC_KSQ_KEEP,
-  KC_MODUP_SMALL, KC_DOWN_SMALL, KC_GEMV_WIN, KC_GEMV_FBC, KC_GEMV_FOLD, KC_GEMV_C0, KC_COUNT
+  KC_MODUP_SMALL, KC_DOWN_SMALL, KC_GEMV_WIN, KC_GEMV_FBC, KC_GEMV_FOLD, KC_GEMV_C0, KC_BSGS_KS, KC_BSGS_INNER,
+  KC_BSGS_SUM, KC_COUNT
 };
 struct ProfScope {
   int cls;
@@ -519,6 +520,23 @@ void k_gemv_batch(uint64_t *y, const uint64_t *x, size_t count, unsigned lvl, co
 void k_gemv_batch_ex(uint64_t *y, size_t y_stride, size_t y_pstride, const uint64_t *x, size_t x_stride,
                      size_t x_pstride, size_t count, unsigned lvl, const double *K, const unsigned *d, unsigned E,
                      int mode);
+// he_gemv_bsgs (bsgs.hip).  One rotation's key-switch inner product: acc0 /
+// acc1 ([2][lvl + K][n]) <- sum_j D_j[perm_g k] evk_j[k] (+ [P] c0[perm_g k]
+// into acc0 on the q limbs), D [ndig][lvl + K][n] the ModUp digits of the
+// rotated ciphertext's c1, evk the key's payload.  jobs_dev: device memory.
+struct BsgsKsJob {
+  const uint64_t *D, *c0, *evk;
+  uint64_t *acc;
+  uint64_t g;
+};
+void k_bsgs_ks(const BsgsKsJob *jobs_dev, unsigned njobs, unsigned lvl, double bytes);
+// U [nj][2][lvl][n] <- u_j = sum_i P[tab[j gs + i]] b_i over the gs baby slots
+// B [gs][2][lvl][n]; P: ndiag encoded diagonals, [lvl][n] each; tab (device):
+// index into P, -1 for none
+void k_bsgs_inner(uint64_t *U, const uint64_t *B, const uint64_t *P, const int *tab_dev, unsigned nj, unsigned gs,
+                  unsigned ndiag, unsigned lvl);
+// out [2][lvl][n] <- base (or 0) + R[0] + .. + R[cnt - 1] (r_stride words apart)
+void k_bsgs_sum(uint64_t *out, const uint64_t *base, const uint64_t *R, unsigned cnt, size_t r_stride, unsigned lvl);
 void tables_upload();
 void tables_prewarm();
 void tables_free();

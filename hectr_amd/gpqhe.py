@@ -149,6 +149,15 @@ NEWER = {"gpqhe_spec_gemv_taken", "gpqhe_spec_dcd_taken"}
 #: symbols declared in include/gpqhe.h (checked by tests/test_abi.py)
 EXPORTED = sorted(SIGNATURES)
 
+#: include/gpqhe_ext.h: exported by the product library only (the oracle has
+#: no restatement of them; tests check them against compositions of the ABI
+#: above).  Bound where the loaded library has them.
+PRODUCT_EXT = {
+    "he_gemv_bsgs": (None, [OBJ, VP, OBJ, OBJ, C.c_uint]),
+    "he_genrk_bsgs": (None, [OBJ, OBJ, C.c_uint]),
+    "he_gemv_bsgs_default_g": (C.c_uint, []),
+}
+
 
 def _cplx(z) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(z, dtype=np.complex128))
@@ -170,6 +179,11 @@ class Engine:
             f = getattr(self.lib, sym)
             f.restype = res
             f.argtypes = args
+        for sym, (res, args) in PRODUCT_EXT.items():
+            if hasattr(self.lib, sym):  # not the oracle, nor an older library under GPQHE_LIB
+                f = getattr(self.lib, sym)
+                f.restype = res
+                f.argtypes = args
         self.info = None
 
     @classmethod
@@ -313,6 +327,23 @@ class Engine:
     def gemv(self, y, M, x, rk):
         M = _cplx(M)
         self.lib.he_gemv(C.byref(y), M.ctypes.data, C.byref(x), rk)
+
+    def _ext(self, sym):
+        if not hasattr(self.lib, sym):
+            raise AttributeError(f"{self.name} library {self.path} does not export {sym} (include/gpqhe_ext.h)")
+        return getattr(self.lib, sym)
+
+    def gemv_bsgs(self, y, M, x, rk, g=0):
+        """y = M x by baby-step giant-step (g = 0: the default baby-step count)."""
+        M = _cplx(M)
+        self._ext("he_gemv_bsgs")(C.byref(y), M.ctypes.data, C.byref(x), rk, g)
+
+    def genrk_bsgs(self, rk, sk, g=0):
+        """The rotation keys gemv_bsgs(.., g) can need, into rk[slots]."""
+        self._ext("he_genrk_bsgs")(rk, C.byref(sk), g)
+
+    def bsgs_default_g(self):
+        return int(self._ext("he_gemv_bsgs_default_g")())
 
     def rot(self, out, x, r, rk):
         self.lib.he_rot(C.byref(out), C.byref(x), r, rk)
