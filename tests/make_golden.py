@@ -1,11 +1,19 @@
-"""Generate tests/golden/model_vectors.json from the pure-Python model only
-(no oracle, no product): prime/root selection rule, NTT by definition,
-exact rescale.  Run: python tests/make_golden.py"""
+"""Generate the committed known-answer vectors.
+
+tests/golden/model_vectors.json comes from the pure-Python model only (no
+oracle, no product): prime/root selection rule, NTT by definition, exact
+rescale.  tests/golden/chacha_vectors.json holds ChaCha20 keystream blocks
+produced by the local `openssl enc -chacha20` (neither the model nor the
+engine), for the (key, stream, counter) triples of CHACHA_CASES.
+Run: python tests/make_golden.py"""
 import json
 import os
 import random
+import shutil
+import subprocess
 
 import ckks_model as M
+import ckks_model_rng as R
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -29,6 +37,29 @@ def psi_of(q, n):
         if pow(p, n, q) == q - 1:
             return p
         h += 1
+
+
+#: (seed or None for the all-zero key, stream, counter)
+CHACHA_CASES = [(None, 0, 0), (None, 0, 1), (1, 0, 0), (1, 2, 5), (99, 7, 2 ** 32 - 1), (99, 2 ** 32, 3),
+                (2024, 2 ** 32 + 5, 2 ** 31), (0xFFFFFFFFFFFFFFFF, 2 ** 64 - 1, 2 ** 32 - 1)]
+
+
+def openssl_block(key, stream, counter):
+    """64 keystream bytes of block (stream, counter) under the eight key words,
+    from `openssl enc -chacha20` over 64 zero bytes."""
+    out = subprocess.run(["openssl", "enc", "-chacha20", "-K", R.key_bytes(key).hex(), "-iv",
+                          R.iv_bytes(stream, counter).hex()], input=bytes(64), stdout=subprocess.PIPE, check=True)
+    assert len(out.stdout) == 64
+    return out.stdout
+
+
+def chacha_vectors():
+    out = []
+    for seed, stream, counter in CHACHA_CASES:
+        key = [0] * 8 if seed is None else R.seed_key(seed)
+        out.append({"seed": seed, "key": key, "stream": stream, "counter": counter,
+                    "keystream": openssl_block(key, stream, counter).hex()})
+    return out
 
 
 def main():
@@ -62,6 +93,12 @@ def main():
     out["rescale"].append({"logn": logn, "primes": used, "input": inp, "output": res})
     with open(os.path.join(HERE, "golden", "model_vectors.json"), "w") as f:
         json.dump(out, f)
+    # last, and only where openssl exists: the pure-model file above needs none
+    if shutil.which("openssl") is None:
+        print("no openssl on the path: tests/golden/chacha_vectors.json left as it is")
+        return
+    with open(os.path.join(HERE, "golden", "chacha_vectors.json"), "w") as f:
+        json.dump({"source": "openssl enc -chacha20, 64 zero bytes in", "blocks": chacha_vectors()}, f, indent=1)
 
 
 if __name__ == "__main__":
