@@ -4,6 +4,7 @@
 // reference src/ctr.c:445-618 and src/hempc.c:216-274 (see gpqhe.h).
 #include "gpqhe_internal.h"
 #include "../../include/gpqhe_ext.h"
+#include "../../include/gpqhe_ext_batch.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -3019,6 +3020,178 @@ extern "C" void he_genrk_bsgs(he_evk_t rk[], const poly_mpi_t *sk, unsigned int 
   }
 }
 
+// ---------------------------------------------------------------------------
+// The stages of a BSGS product, shared by he_gemv_bsgs and he_gemv_bsgs_batch
+// (include/gpqhe_ext_batch.h).  A stage writes its slots (baby slots, rotated
+// giant steps) `stride` words apart: 2 lvl n for the single call's packed
+// buffers, cnt 2 lvl n for a chunk's slot-major ones.
+// ---------------------------------------------------------------------------
+// What keeps a plan that is not in the cache alive for one call.
+struct BsgsPlanHold {
+  BsgsPlan tmp;
+  std::unique_ptr<Ws> pts, tab;
+};
+
+// The encoded diagonals of (M, lvl, g): cached, or (a set larger than the
+// cache, or the zero matrix) in the holder.  One compare of M per call; every
+// eviction happens here, before the call's first launch.
+static const BsgsPlan *bsgs_plan_get(BsgsPlanHold &h, const double *Md, unsigned lvl, unsigned g)
+{
+  const unsigned s = G.slots;
+  const size_t pw = (size_t)lvl * G.n, mwords = 2 * (size_t)s * s;
+  for (auto it = g_bsgs.begin(); it != g_bsgs.end(); ++it)
+    if (it->s == s && it->lvl == lvl && it->g == g && !memcmp(it->M.data(), Md, mwords * 8)) {
+      g_bsgs.splice(g_bsgs.begin(), g_bsgs, it);
+      return &g_bsgs.front();
+    }
+  BsgsPlan &tmp = h.tmp;
+  bsgs_plan(tmp, Md, g);
+  const size_t tabw = (tmp.tab.size() * sizeof(int) + 7) / 8;
+  tmp.bytes = tmp.ds.size() * pw * 8;
+  if (tmp.bytes > diag_cache_cap()) {
+    h.pts.reset(new Ws(tmp.ds.size() * pw));
+    h.tab.reset(new Ws(tabw));
+    tmp.pts = h.pts->p;
+    tmp.tab_dev = (int *)h.tab->p;
+  } else if (!tmp.ds.empty()) {
+    while (!g_bsgs.empty() && g_bsgs_bytes + tmp.bytes > diag_cache_cap()) {
+      pool_free(g_bsgs.back().pts);
+      pool_free(g_bsgs.back().tab_dev);
+      g_bsgs_bytes -= g_bsgs.back().bytes;
+      g_bsgs.pop_back();
+    }
+    tmp.pts = (uint64_t *)pool_alloc(tmp.bytes);
+    tmp.tab_dev = (int *)pool_alloc(tabw * 8);
+  }
+  if (!tmp.ds.empty()) {
+    bsgs_encode(tmp, Md, lvl, g, tmp.pts);
+    upload(tmp.tab_dev, tmp.tab.data(), tmp.tab.size() * sizeof(int));
+  }
+  if (h.pts || tmp.ds.empty())
+    return &tmp;
+  tmp.M.assign(Md, Md + mwords);  // the owned copy: made on a miss only
+  tmp.s = s;
+  tmp.lvl = lvl;
+  tmp.g = g;
+  g_bsgs_bytes += tmp.bytes;
+  g_bsgs.push_front(std::move(tmp));
+  return &g_bsgs.front();
+}
+
+// Every rotation a plan uses and its key (found before anything is launched).
+struct BsgsKeys {
+  unsigned nbs, nj;      // baby slots, giant steps
+  unsigned has0, nbr;    // slot 0 is x itself; rotated baby slots
+  unsigned hasj0, njr;   // giant step 0 is not rotated; rotated giant steps
+  std::vector<unsigned> brot, grot;
+  std::vector<const he_evk_t *> bkey, gkey;
+  std::vector<uint64_t> bgal, ggal;
+};
+
+static BsgsKeys bsgs_find_keys(const BsgsPlan &plan, const he_evk_t rk[], unsigned g)
+{
+  BsgsKeys k;
+  k.nbs = (unsigned)plan.baby.size();
+  k.nj = (unsigned)plan.giant.size();
+  k.has0 = plan.baby[0] == 0;
+  k.nbr = k.nbs - k.has0;
+  k.hasj0 = plan.giant[0] == 0;
+  k.njr = k.nj - k.hasj0;
+  k.brot.resize(k.nbr);
+  k.bkey.resize(k.nbr);
+  k.bgal.resize(k.nbr);
+  k.grot.resize(k.njr);
+  k.gkey.resize(k.njr);
+  k.ggal.resize(k.njr);
+  for (unsigned r = 0; r < k.nbr; r++) {
+    k.brot[r] = plan.baby[k.has0 + r];
+    k.bgal[r] = galois_of_rot(k.brot[r]);
+    k.bkey[r] = find_rot_key(rk, k.brot[r], k.bgal[r]);
+  }
+  for (unsigned r = 0; r < k.njr; r++) {
+    k.grot[r] = plan.giant[k.hasj0 + r] * g;
+    k.ggal[r] = galois_of_rot(k.grot[r]);
+    k.gkey[r] = find_rot_key(rk, k.grot[r], k.ggal[r]);
+  }
+  return k;
+}
+
+// ModDown by P of cnt rotations' accumulators into slots `stride` words
+// apart: one launch where the slots are packed, else one per rotation.
+static void bsgs_down(uint64_t *out, size_t stride, uint64_t *acc, unsigned cnt, unsigned lvl)
+{
+  const unsigned nm = lvl + G.K;
+  const size_t n = G.n, pw = (size_t)lvl * n, accw = 2 * (size_t)nm * n;
+  if (stride == 2 * pw || cnt == 1) {
+    k_moddown(out, pw, acc, (size_t)nm * n, 2 * cnt, lvl, 0);
+    return;
+  }
+  for (unsigned t = 0; t < cnt; t++)
+    k_moddown(out + t * stride, pw, acc + t * accw, (size_t)nm * n, 2, lvl, 0);
+}
+
+// Baby stage of one ciphertext: slot i of B <- rot(x, baby[i]), slot 0 x
+// itself where diagonals use it.  One hoisted ModUp, rotations in chunks whose
+// accumulators fit the budget.
+static void bsgs_baby(uint64_t *B, size_t stride, const he_ct_t *x, const BsgsKeys &k, unsigned lvl, size_t budget)
+{
+  const unsigned nm = lvl + G.K, ndig = (lvl + G.alpha - 1) / G.alpha;
+  const size_t n = G.n, pw = (size_t)lvl * n, accw = 2 * (size_t)nm * n, dw = (size_t)ndig * nm * n;
+  if (k.has0)
+    for (unsigned p = 0; p < 2; p++)
+      HIP_CHECK(hipMemcpyAsync(B + p * pw, limb(x, p, 0), pw * 8, hipMemcpyDeviceToDevice, G.stream));
+  if (!k.nbr)
+    return;
+  const unsigned cb = (unsigned)std::min<size_t>(k.nbr, std::max<size_t>(1, budget / accw));
+  Ws D(dw), acc((size_t)cb * accw);
+  hoist_modup(D.p, x, lvl);
+  for (unsigned r0 = 0; r0 < k.nbr; r0 += cb) {
+    const unsigned cnt = std::min(cb, k.nbr - r0);
+    std::vector<BsgsKsJob> jobs(cnt);
+    for (unsigned t = 0; t < cnt; t++)
+      jobs[t] = BsgsKsJob{D.p, limb(x, 0, 0), k.bkey[r0 + t]->data, acc.p + t * accw, k.bgal[r0 + t]};
+    bsgs_ks_launch(jobs, lvl, true);
+    bsgs_down(B + (size_t)(k.has0 + r0) * stride, stride, acc.p, cnt, lvl);
+  }
+}
+
+// Words of key-switch workspace one giant step holds (its ModUp digits and
+// accumulators), and how many fit the budget next to `extra` words each.
+static unsigned bsgs_giant_chunk(const BsgsKeys &k, unsigned lvl, size_t budget, size_t extra)
+{
+  const unsigned nm = lvl + G.K, ndig = (lvl + G.alpha - 1) / G.alpha;
+  const size_t n = G.n, accw = 2 * (size_t)nm * n, dw = (size_t)ndig * nm * n;
+  return (unsigned)std::min<size_t>(k.njr, std::max<size_t>(1, budget / (dw + accw + extra)));
+}
+
+// Giant stage of one ciphertext, rotated giant steps [r0, r0 + cnt): u of step
+// r at U + (hasj0 + r) u_stride, its rotation by giant[r] g into R + (r - r0)
+// r_stride.  Dg [cnt][ndig][nm][n] and acc [cnt][2][nm][n] are workspace.
+static void bsgs_giant(uint64_t *R, size_t r_stride, const uint64_t *U, size_t u_stride, const BsgsKeys &k,
+                       unsigned r0, unsigned cnt, unsigned lvl, uint64_t *Dg, uint64_t *acc)
+{
+  const unsigned nm = lvl + G.K, ndig = (lvl + G.alpha - 1) / G.alpha;
+  const size_t n = G.n, pw = (size_t)lvl * n, accw = 2 * (size_t)nm * n, dw = (size_t)ndig * nm * n;
+  const uint64_t *u = U + (size_t)(k.hasj0 + r0) * u_stride;
+  for (unsigned b0 = 0; b0 < cnt; b0 += XPtrs::MAX) {
+    const unsigned c = std::min(XPtrs::MAX, cnt - b0);
+    XPtrs x1{};
+    for (unsigned t = 0; t < c; t++)
+      x1.p[t] = u + (size_t)(b0 + t) * u_stride + pw;
+    k_modup_ntt(Dg + b0 * dw, x1, c, dw, lvl);
+  }
+  std::vector<BsgsKsJob> jobs(cnt);
+  for (unsigned t = 0; t < cnt; t++)
+    jobs[t] = BsgsKsJob{Dg + t * dw, u + (size_t)t * u_stride, k.gkey[r0 + t]->data, acc + t * accw, k.ggal[r0 + t]};
+  bsgs_ks_launch(jobs, lvl, false);
+  bsgs_down(R, r_stride, acc, cnt, lvl);
+}
+
+static size_t bsgs_budget()
+{
+  return ((size_t)env_u("GPQHE_WS_MIB", 8192) << 20) / 8;  // words per key-switch workspace
+}
+
 extern "C" void he_gemv_bsgs(he_ct_t *y, const gpqhe_complex_t M[], const he_ct_t *x, const he_evk_t rk[],
                              unsigned int g)
 {
@@ -3031,59 +3204,11 @@ extern "C" void he_gemv_bsgs(he_ct_t *y, const gpqhe_complex_t M[], const he_ct_
     gpqhe_die("he_gemv_bsgs: g = %u > slots = %u", g, s);
   if (lvl < 2)
     gpqhe_die("he_gemv_bsgs: input at the lowest level");
-  const double *Md = (const double *)M;
-  const unsigned nm = lvl + G.K, ndig = (lvl + G.alpha - 1) / G.alpha;
-  const size_t n = G.n, pw = (size_t)lvl * n, accw = 2 * (size_t)nm * n, dw = (size_t)ndig * nm * n;
-  const size_t budget = ((size_t)env_u("GPQHE_WS_MIB", 8192) << 20) / 8;  // words per key-switch workspace
+  const size_t n = G.n, pw = (size_t)lvl * n;
+  const size_t budget = bsgs_budget();
 
-  // the encoded diagonals: cached, or (a set larger than the cache) in workspace
-  const BsgsPlan *plan = nullptr;
-  BsgsPlan tmp;
-  std::unique_ptr<Ws> tmp_pts, tmp_tab;
-  {
-    const size_t mwords = 2 * (size_t)s * s;
-    for (auto it = g_bsgs.begin(); it != g_bsgs.end(); ++it)
-      if (it->s == s && it->lvl == lvl && it->g == g && !memcmp(it->M.data(), Md, mwords * 8)) {
-        g_bsgs.splice(g_bsgs.begin(), g_bsgs, it);
-        plan = &g_bsgs.front();
-        break;
-      }
-    if (!plan) {
-      bsgs_plan(tmp, Md, g);
-      const size_t tabw = (tmp.tab.size() * sizeof(int) + 7) / 8;
-      tmp.bytes = tmp.ds.size() * pw * 8;
-      if (tmp.bytes > diag_cache_cap()) {
-        tmp_pts.reset(new Ws(tmp.ds.size() * pw));
-        tmp_tab.reset(new Ws(tabw));
-        tmp.pts = tmp_pts->p;
-        tmp.tab_dev = (int *)tmp_tab->p;
-      } else if (!tmp.ds.empty()) {
-        while (!g_bsgs.empty() && g_bsgs_bytes + tmp.bytes > diag_cache_cap()) {
-          pool_free(g_bsgs.back().pts);
-          pool_free(g_bsgs.back().tab_dev);
-          g_bsgs_bytes -= g_bsgs.back().bytes;
-          g_bsgs.pop_back();
-        }
-        tmp.pts = (uint64_t *)pool_alloc(tmp.bytes);
-        tmp.tab_dev = (int *)pool_alloc(tabw * 8);
-      }
-      if (!tmp.ds.empty()) {
-        bsgs_encode(tmp, Md, lvl, g, tmp.pts);
-        upload(tmp.tab_dev, tmp.tab.data(), tmp.tab.size() * sizeof(int));
-      }
-      if (tmp_pts || tmp.ds.empty()) {
-        plan = &tmp;
-      } else {
-        tmp.M.assign(Md, Md + mwords);  // the owned copy: made on a miss only
-        tmp.s = s;
-        tmp.lvl = lvl;
-        tmp.g = g;
-        g_bsgs_bytes += tmp.bytes;
-        g_bsgs.push_front(std::move(tmp));
-        plan = &g_bsgs.front();
-      }
-    }
-  }
+  BsgsPlanHold hold;
+  const BsgsPlan *plan = bsgs_plan_get(hold, (const double *)M, lvl, g);
   prov_forget(y->data, pstride(y));
   if (plan->ds.empty()) {  // all-zero matrix
     for (unsigned p = 0; p < 2; p++)
@@ -3091,67 +3216,28 @@ extern "C" void he_gemv_bsgs(he_ct_t *y, const gpqhe_complex_t M[], const he_ct_
     gemv_set_meta(y, x, lvl);
     return;
   }
-  const unsigned nbs = (unsigned)plan->baby.size(), nj = (unsigned)plan->giant.size();
-  const unsigned has0 = plan->baby[0] == 0, nbr = nbs - has0;
-  const unsigned hasj0 = plan->giant[0] == 0, njr = nj - hasj0;
-  // every key this call reads, before anything is launched
-  std::vector<const he_evk_t *> bkey(nbr), gkey(njr);
-  std::vector<uint64_t> bgal(nbr), ggal(njr);
-  for (unsigned r = 0; r < nbr; r++) {
-    bgal[r] = galois_of_rot(plan->baby[has0 + r]);
-    bkey[r] = find_rot_key(rk, plan->baby[has0 + r], bgal[r]);
-  }
-  for (unsigned r = 0; r < njr; r++) {
-    ggal[r] = galois_of_rot(plan->giant[hasj0 + r] * g);
-    gkey[r] = find_rot_key(rk, plan->giant[hasj0 + r] * g, ggal[r]);
-  }
+  const BsgsKeys k = bsgs_find_keys(*plan, rk, g);
 
-  // baby steps: B [nbs][2][lvl][n], slot 0 x itself where diagonals use it
-  Ws B((size_t)nbs * 2 * pw);
-  if (has0)
-    for (unsigned p = 0; p < 2; p++)
-      HIP_CHECK(hipMemcpyAsync(B.p + p * pw, limb(x, p, 0), pw * 8, hipMemcpyDeviceToDevice, G.stream));
-  if (nbr) {
-    const unsigned cb = (unsigned)std::min<size_t>(nbr, std::max<size_t>(1, budget / accw));
-    Ws D(dw), acc((size_t)cb * accw);
-    hoist_modup(D.p, x, lvl);
-    for (unsigned r0 = 0; r0 < nbr; r0 += cb) {
-      const unsigned cnt = std::min(cb, nbr - r0);
-      std::vector<BsgsKsJob> jobs(cnt);
-      for (unsigned t = 0; t < cnt; t++)
-        jobs[t] = BsgsKsJob{D.p, limb(x, 0, 0), bkey[r0 + t]->data, acc.p + t * accw, bgal[r0 + t]};
-      bsgs_ks_launch(jobs, lvl, true);
-      k_moddown(B.p + (size_t)(has0 + r0) * 2 * pw, pw, acc.p, (size_t)nm * n, 2 * cnt, lvl, 0);
-    }
-  }
+  // baby steps: B [nbs][2][lvl][n]
+  Ws B((size_t)k.nbs * 2 * pw);
+  bsgs_baby(B.p, 2 * pw, x, k, lvl, budget);
 
   // the plaintext inner sums: U [nj][2][lvl][n]
-  Ws U((size_t)nj * 2 * pw);
-  k_bsgs_inner(U.p, B.p, plan->pts, plan->tab_dev, nj, nbs, (unsigned)plan->ds.size(), lvl);
+  Ws U((size_t)k.nj * 2 * pw);
+  k_bsgs_inner(U.p, B.p, plan->pts, plan->tab_dev, k.nj, k.nbs, (unsigned)plan->ds.size(), lvl);
 
   // giant steps: each u_j (j >= 1) rotated by j g through its own ModDown,
   // then summed (with u_0) over the q limbs; chunks of cg giant steps
   uint64_t *S = U.p;
-  Ws Sw(njr ? 2 * pw : 0);
-  if (njr) {
-    const unsigned cg = (unsigned)std::min<size_t>(njr, std::max<size_t>(1, budget / (dw + accw + 2 * pw)));
-    Ws Dg((size_t)cg * dw), acc((size_t)cg * accw), R((size_t)cg * 2 * pw);
-    const uint64_t *base = hasj0 ? U.p : nullptr;
-    for (unsigned r0 = 0; r0 < njr; r0 += cg) {
-      const unsigned cnt = std::min(cg, njr - r0);
-      const uint64_t *u = U.p + (size_t)(hasj0 + r0) * 2 * pw;
-      for (unsigned b0 = 0; b0 < cnt; b0 += XPtrs::MAX) {
-        const unsigned c = std::min(XPtrs::MAX, cnt - b0);
-        XPtrs x1{};
-        for (unsigned t = 0; t < c; t++)
-          x1.p[t] = u + (size_t)(b0 + t) * 2 * pw + pw;
-        k_modup_ntt(Dg.p + b0 * dw, x1, c, dw, lvl);
-      }
-      std::vector<BsgsKsJob> jobs(cnt);
-      for (unsigned t = 0; t < cnt; t++)
-        jobs[t] = BsgsKsJob{Dg.p + t * dw, u + (size_t)t * 2 * pw, gkey[r0 + t]->data, acc.p + t * accw, ggal[r0 + t]};
-      bsgs_ks_launch(jobs, lvl, false);
-      k_moddown(R.p, pw, acc.p, (size_t)nm * n, 2 * cnt, lvl, 0);
+  Ws Sw(k.njr ? 2 * pw : 0);
+  if (k.njr) {
+    const unsigned nm = lvl + G.K, ndig = (lvl + G.alpha - 1) / G.alpha;
+    const unsigned cg = bsgs_giant_chunk(k, lvl, budget, 2 * pw);
+    Ws Dg((size_t)cg * ndig * nm * n), acc((size_t)cg * 2 * nm * n), R((size_t)cg * 2 * pw);
+    const uint64_t *base = k.hasj0 ? U.p : nullptr;
+    for (unsigned r0 = 0; r0 < k.njr; r0 += cg) {
+      const unsigned cnt = std::min(cg, k.njr - r0);
+      bsgs_giant(R.p, 2 * pw, U.p, 2 * pw, k, r0, cnt, lvl, Dg.p, acc.p);
       k_bsgs_sum(Sw.p, base, R.p, cnt, 2 * pw, lvl);
       base = Sw.p;
     }
@@ -3273,11 +3359,35 @@ static size_t fold_cap()
   return cap;
 }
 
+// The folded rotation keys of he_gemv_bsgs_batch: one entry per (key array,
+// key generation, level, rotation), most recently used first, bounded in
+// bytes by fold_cap() -- a cache apart from g_folds, whose eight entries a
+// BSGS call's 30 rotations would turn over on every call.  A call holds an
+// entry only while the launches that read it are issued (RotFoldUse).
+struct RotFold {
+  const he_evk_t *rk;
+  uint64_t gen;
+  unsigned lvl, rot;
+  double *K;
+  size_t bytes;
+};
+static std::list<RotFold> g_rfolds;
+static size_t g_rfold_bytes = 0;
+static const double *g_rfold_inuse = nullptr;
+struct RotFoldUse {
+  explicit RotFoldUse(const RotFold &f) { g_rfold_inuse = f.K; }
+  ~RotFoldUse() { g_rfold_inuse = nullptr; }
+};
+
 static void fold_cache_clear()
 {
   for (FoldEntry &f : g_folds)
     pool_free(f.K);
   g_folds.clear();
+  for (RotFold &f : g_rfolds)
+    pool_free(f.K);
+  g_rfolds.clear();
+  g_rfold_bytes = 0;
 }
 
 // out of memory: every set no running call reads goes back to the pool
@@ -3287,6 +3397,14 @@ static void fold_cache_trim()
     if (it->K != g_fold_inuse) {
       pool_free(it->K);
       it = g_folds.erase(it);
+    } else {
+      ++it;
+    }
+  for (auto it = g_rfolds.begin(); it != g_rfolds.end();)
+    if (it->K != g_rfold_inuse) {
+      pool_free(it->K);
+      g_rfold_bytes -= it->bytes;
+      it = g_rfolds.erase(it);
     } else {
       ++it;
     }
@@ -3409,6 +3527,38 @@ static bool rot_batch_fast(uint64_t *out, const uint64_t *x, size_t count, unsig
   return true;
 }
 
+// The key of rotation r folded for level lvl (he_gemv_bsgs_batch).  Entries
+// of an older key generation never match and are released at the next miss;
+// the least recently used go while the cache would exceed its cap.
+static const RotFold &bsgs_rot_fold(unsigned r, unsigned lvl, const he_evk_t rk[])
+{
+  const he_evk_t *k = find_rot_key(rk, r, galois_of_rot(r));
+  for (auto it = g_rfolds.begin(); it != g_rfolds.end(); ++it)
+    if (it->rot == r && it->lvl == lvl && it->gen == g_key_gen && it->rk == rk) {
+      g_rfolds.splice(g_rfolds.begin(), g_rfolds, it);
+      return g_rfolds.front();
+    }
+  const size_t bytes = k_gemv_fold_words(1, lvl) * 8;
+  for (auto it = g_rfolds.begin(); it != g_rfolds.end();)
+    if (it->gen != g_key_gen) {  // folded with keys that changed since
+      pool_free(it->K);
+      g_rfold_bytes -= it->bytes;
+      it = g_rfolds.erase(it);
+    } else {
+      ++it;
+    }
+  while (!g_rfolds.empty() && g_rfold_bytes + bytes > fold_cap()) {
+    pool_free(g_rfolds.back().K);
+    g_rfold_bytes -= g_rfolds.back().bytes;
+    g_rfolds.pop_back();
+  }
+  const GemvDiagIn dg{r, nullptr, k->data};
+  double *K = k_gemv_fold(&dg, 1, lvl);  // (an out-of-memory retry inside may empty the list)
+  g_rfolds.push_front(RotFold{rk, g_key_gen, lvl, r, K, bytes});
+  g_rfold_bytes += bytes;
+  return g_rfolds.front();
+}
+
 // A ciphertext of a batch as an object view (no payload of its own).
 static he_ct_t ct_view(const uint64_t *base, unsigned nlimbs)
 {
@@ -3455,6 +3605,115 @@ extern "C" void he_rot_batch(uint64_t *out, const uint64_t *x, size_t count, uns
   for (size_t i = 0; i < count; i++) {
     he_ct_t cx = ct_view(x + i * words, lvl), co = ct_view(out + i * words, lvl);
     he_rot(&co, &cx, rot, rk);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// he_gemv_bsgs_batch (include/gpqhe_ext_batch.h): he_gemv_bsgs over count
+// ciphertexts that share M, g and the keys.  One plan lookup per call; the
+// ciphertexts in chunks that fit GPQHE_WS_MIB; inside a chunk the buffers are
+// slot-major -- B [baby slot][ct][2][lvl][n], U and R [giant step][ct][2][lvl][n]
+// -- so a rotation of the whole chunk is one contiguous batch for the windowed
+// path (k_gemv_batch with the rotation's fold, as he_rot_batch), and the inner
+// sums share every encoded diagonal word among a tile of ciphertexts
+// (bsgs_inner_batch_kernel).  Where the windowed path is off, the single
+// call's hoisted stages run per ciphertext into the same buffers.  Every step
+// gives the residues of he_gemv_bsgs's.
+// ---------------------------------------------------------------------------
+static void bsgs_batch_chunk(uint64_t *y, const uint64_t *x, unsigned cnt, unsigned lvl, const BsgsPlan &plan,
+                             const BsgsKeys &k, const he_evk_t rk[], size_t budget)
+{
+  const unsigned nm = lvl + G.K, ndig = (lvl + G.alpha - 1) / G.alpha;
+  const size_t n = G.n, pw = (size_t)lvl * n, cw = 2 * pw, sw = (size_t)cnt * cw;  // words: ciphertext, slot
+  const bool win = gemv_win_on(lvl);
+  Ws B((size_t)k.nbs * sw), U((size_t)k.nj * sw), R((size_t)k.njr * sw);
+
+  // baby steps
+  if (win) {
+    if (k.has0)
+      HIP_CHECK(hipMemcpyAsync(B.p, x, sw * 8, hipMemcpyDeviceToDevice, G.stream));
+    for (unsigned r = 0; r < k.nbr; r++) {
+      const RotFold &f = bsgs_rot_fold(k.brot[r], lvl, rk);
+      RotFoldUse use(f);
+      k_gemv_batch(B.p + (size_t)(k.has0 + r) * sw, x, cnt, lvl, f.K, &f.rot, 1, 0);
+    }
+  } else {
+    for (unsigned c = 0; c < cnt; c++) {
+      const he_ct_t cx = ct_view(x + c * cw, lvl);
+      bsgs_baby(B.p + c * cw, sw, &cx, k, lvl, budget);
+    }
+  }
+
+  // the inner sums of every ciphertext
+  k_bsgs_inner_batch(U.p, B.p, plan.pts, plan.tab_dev, k.nj, k.nbs, (unsigned)plan.ds.size(), lvl, cnt);
+
+  // giant steps: u_j of the whole chunk rotated by j g into R
+  if (win) {
+    for (unsigned r = 0; r < k.njr; r++) {
+      const RotFold &f = bsgs_rot_fold(k.grot[r], lvl, rk);
+      RotFoldUse use(f);
+      k_gemv_batch(R.p + (size_t)r * sw, U.p + (size_t)(k.hasj0 + r) * sw, cnt, lvl, f.K, &f.rot, 1, 0);
+    }
+  } else if (k.njr) {
+    const unsigned cg = bsgs_giant_chunk(k, lvl, budget, 0);
+    Ws Dg((size_t)cg * ndig * nm * n), acc((size_t)cg * 2 * nm * n);
+    for (unsigned c = 0; c < cnt; c++)
+      for (unsigned r0 = 0; r0 < k.njr; r0 += cg)
+        bsgs_giant(R.p + (size_t)r0 * sw + c * cw, sw, U.p + c * cw, sw, k, r0, std::min(cg, k.njr - r0), lvl, Dg.p,
+                   acc.p);
+  }
+
+  // sum over the giant steps (u_0 is not rotated) and rescale by q_top into y
+  uint64_t *S = U.p;
+  Ws Sw(k.njr ? sw : 0);
+  if (k.njr) {
+    k_bsgs_sum_batch(Sw.p, k.hasj0 ? U.p : nullptr, R.p, k.njr, sw, lvl, cnt);
+    S = Sw.p;
+  }
+  k_moddown(y, (size_t)(lvl - 1) * n, S, pw, 2 * cnt, lvl, 2);
+}
+
+extern "C" void he_gemv_bsgs_batch(uint64_t *y, const gpqhe_complex_t M[], const uint64_t *x, size_t count,
+                                   unsigned int nlimbs, const he_evk_t rk[], unsigned int g)
+{
+  HPROF("gemv_bsgs_batch");
+  check_ctx();
+  const unsigned s = G.slots, lvl = nlimbs;
+  if (lvl < 2 || lvl > G.L)
+    gpqhe_die("he_gemv_bsgs_batch: bad level %u", lvl);
+  if (!g)
+    g = bsgs_default_g();
+  if (g > s)
+    gpqhe_die("he_gemv_bsgs_batch: g = %u > slots = %u", g, s);
+  const unsigned nm = lvl + G.K, ndig = (lvl + G.alpha - 1) / G.alpha;
+  const size_t n = G.n, pw = (size_t)lvl * n, in_words = 2 * pw, out_words = 2 * (size_t)(lvl - 1) * n;
+  if (!count)
+    return;
+  if (y < x + count * in_words && x < y + count * out_words)
+    gpqhe_die("he_gemv_bsgs_batch: output overlaps the input");
+
+  BsgsPlanHold hold;
+  const BsgsPlan *plan = bsgs_plan_get(hold, (const double *)M, lvl, g);
+  if (plan->ds.empty()) {  // all-zero matrix
+    HIP_CHECK(hipMemsetAsync(y, 0, count * out_words * 8, G.stream));
+    return;
+  }
+  const BsgsKeys k = bsgs_find_keys(*plan, rk, g);
+
+  // a ciphertext's share of a chunk: its baby slots, giant steps, rotated
+  // giants and sum, and on the windowed path k_gemv_batch's workspace (the
+  // generic stages' workspaces do not grow with the chunk)
+  const size_t budget = bsgs_budget();
+  const size_t per_ct = (size_t)(k.nbs + k.nj + k.njr + 1) * 2 * pw +
+                        (gemv_win_on(lvl) ? ((size_t)lvl + (size_t)ndig * nm + 2 * (size_t)nm) * n : 0);
+  size_t chunk = std::min<size_t>(std::max<size_t>(1, budget / per_ct), 16384);
+  if (const char *e = getenv("GPQHE_BSGS_CHUNK"))  // test hook: several chunks on a small batch
+    chunk = std::max<size_t>(1, std::min<size_t>(chunk, strtoul(e, nullptr, 0)));
+  else  // equal chunks: a short last one runs at a fraction of the GPU's width
+    chunk = (count + (count + chunk - 1) / chunk - 1) / ((count + chunk - 1) / chunk);
+  for (size_t c0 = 0; c0 < count; c0 += chunk) {
+    const unsigned cnt = (unsigned)std::min(chunk, count - c0);
+    bsgs_batch_chunk(y + c0 * out_words, x + c0 * in_words, cnt, lvl, *plan, k, rk, budget);
   }
 }
 

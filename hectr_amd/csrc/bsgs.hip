@@ -5,6 +5,10 @@
 //   bsgs_ks_kernel     the key-switch inner products of a list of rotations
 //   bsgs_inner_kernel  the plaintext inner sums u_j = sum_i P_j,i b_i
 //   bsgs_sum_kernel    the sum of the rotated giant steps
+// and the two of he_gemv_bsgs_batch (include/gpqhe_ext_batch.h) over a chunk
+// of ciphertexts in slot-major buffers:
+//   bsgs_inner_batch_kernel  the inner sums, a P word shared by a ciphertext tile
+//   bsgs_sum_batch_kernel    the sum of the rotated giant steps of every ciphertext
 #include "gpqhe_internal.h"
 
 #define TPB 256
@@ -186,5 +190,157 @@ void k_bsgs_sum(uint64_t *out, const uint64_t *base, const uint64_t *R, unsigned
   ProfScope ps(KC_BSGS_SUM, 8.0 * total * (cnt + (base ? 2 : 1)));
   hipLaunchKernelGGL(bsgs_sum_kernel, dim3((unsigned)((total / 2 + TPB - 1) / TPB)), dim3(TPB), 0, G.stream, out, base,
                      R, cnt, r_stride, lvl, G.logn, G.dev.mc);
+  HIP_CHECK(hipGetLastError());
+}
+
+// The inner sums of a chunk of cnt ciphertexts: B [gs][cnt][2][lvl][n] ->
+// U [nj][cnt][2][lvl][n], u_{c,j} = sum_i P[tab[j][i]] b_{c,i} as above.  A
+// thread owns one (limb, coefficient) of a tile of CB ciphertexts (grid z):
+// the baby words of TB slots of those CB ciphertexts stay in its registers
+// over the j loop, and every P word it loads serves all CB of them, so P moves
+// once per tile and not once per ciphertext.  Words per ciphertext and (limb,
+// coefficient): ndiag / CB + 2 gs + 2 nj (2 ceil(gs / TB) - 1).  The last
+// tile of a chunk may be partial: its missing ciphertexts load nothing and
+// store nothing (wave-uniform).  128-bit sums, one reduction per output, later
+// baby tiles add to what the same thread wrote.
+// grid: (n / TPB, lvl, ceil(cnt / CB)).
+template <int TB, int CB>
+__global__ void __launch_bounds__(TPB) bsgs_inner_batch_kernel(uint64_t *U, const uint64_t *B, const uint64_t *P,
+                                                               const int *tab, unsigned nj, unsigned gs, unsigned lvl,
+                                                               unsigned logn, unsigned cnt, const ModConst *mc)
+{
+  const size_t n = (size_t)1 << logn;
+  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n)
+    return;
+  const unsigned l = blockIdx.y, c0 = blockIdx.z * CB;
+  const ModConst m = mc[l];
+  const size_t pw = (size_t)lvl << logn;  // words of one polynomial
+  const size_t sw = (size_t)cnt * 2 * pw;  // words of one slot (baby or giant) of the chunk
+  const size_t lo = (size_t)c0 * 2 * pw + ((size_t)l << logn) + k;
+  for (unsigned i0 = 0; i0 < gs; i0 += TB) {
+    uint64_t b0[CB][TB], b1[CB][TB];
+#pragma unroll
+    for (int cc = 0; cc < CB; cc++)
+#pragma unroll
+      for (int ii = 0; ii < TB; ii++) {
+        b0[cc][ii] = b1[cc][ii] = 0;
+        if (i0 + ii < gs && c0 + cc < cnt) {
+          const uint64_t *b = B + (size_t)(i0 + ii) * sw + (size_t)cc * 2 * pw + lo;
+          b0[cc][ii] = b[0];
+          b1[cc][ii] = b[pw];
+        }
+      }
+    for (unsigned j = 0; j < nj; j++) {
+      const int *tj = tab + (size_t)j * gs + i0;
+      unsigned __int128 a0[CB], a1[CB];
+#pragma unroll
+      for (int cc = 0; cc < CB; cc++)
+        a0[cc] = a1[cc] = 0;
+      bool any = false;
+#pragma unroll
+      for (int h = 0; h < TB; h += 8) {
+        uint64_t w[8];
+        int e[8];
+#pragma unroll
+        for (int ii = 0; ii < 8; ii++) {
+          e[ii] = i0 + h + ii < gs ? tj[h + ii] : -1;  // (wave-uniform)
+          w[ii] = 0;
+          if (e[ii] >= 0)
+            w[ii] = P[(size_t)e[ii] * pw + ((size_t)l << logn) + k];
+        }
+#pragma unroll
+        for (int ii = 0; ii < 8; ii++)
+          if (e[ii] >= 0) {
+            any = true;
+#pragma unroll
+            for (int cc = 0; cc < CB; cc++) {
+              a0[cc] += (unsigned __int128)w[ii] * b0[cc][h + ii];
+              a1[cc] += (unsigned __int128)w[ii] * b1[cc][h + ii];
+            }
+          }
+      }
+      if (i0 && !any)
+        continue;
+#pragma unroll
+      for (int cc = 0; cc < CB; cc++) {
+        if (c0 + cc >= cnt)
+          continue;
+        uint64_t *u = U + (size_t)j * sw + (size_t)cc * 2 * pw + lo;
+        uint64_t r0 = bsgs_red128(a0[cc], m), r1 = bsgs_red128(a1[cc], m);
+        if (i0) {
+          r0 = add_mod(r0, u[0], m.q);
+          r1 = add_mod(r1, u[pw], m.q);
+        }
+        u[0] = r0;
+        u[pw] = r1;
+      }
+    }
+  }
+}
+
+// The tile form.  CB = 2; TB = 8 (the single kernel's 32 baby words: 116
+// VGPRs, 4 waves / SIMD) up to 8 baby slots, where a wider tile is half empty,
+// and TB = 16 (182 VGPRs, 2 waves / SIMD) above: same box, 16 ciphertexts at
+// N = 2^16, L = 8, the kernel alone took 901 against 1217 us at 8 baby slots,
+// 3659 against 3463 us at 16 and 15546 against 14658 us at 32
+// (profiles/bsgs_batch_time.json).  GPQHE_BSGS_INNER_TB = 8 or 16 (read per
+// call) forces one form for such A/Bs.
+#define BSGS_BATCH_CB 2
+void k_bsgs_inner_batch(uint64_t *U, const uint64_t *B, const uint64_t *P, const int *tab_dev, unsigned nj, unsigned gs,
+                        unsigned ndiag, unsigned lvl, unsigned cnt)
+{
+  if (!nj || !gs || !cnt)
+    gpqhe_die("k_bsgs_inner_batch: %u giant steps, %u baby slots, %u ciphertexts", nj, gs, cnt);
+  const unsigned ctiles = (cnt + BSGS_BATCH_CB - 1) / BSGS_BATCH_CB;
+  if (ctiles > 65535)
+    gpqhe_die("k_bsgs_inner_batch: %u ciphertexts in one chunk", cnt);
+  const char *e = getenv("GPQHE_BSGS_INNER_TB");
+  const unsigned forced = e ? (unsigned)atoi(e) : 0;
+  const unsigned tb = forced == 8 || forced == 16 ? forced : gs > 8 ? 16 : 8, tiles = (gs + tb - 1) / tb;
+  // every P word once per ciphertext tile; per ciphertext the baby words once
+  // per baby tile, u written once (and re-read and re-written by each later tile)
+  ProfScope ps(KC_BSGS_INNER_BATCH,
+               8.0 * G.n * lvl * ((double)ndiag * ctiles + (double)cnt * (2.0 * gs + 2.0 * nj * (2 * tiles - 1))));
+  const dim3 grid((G.n + TPB - 1) / TPB, lvl, ctiles);
+  if (tb == 16)
+    hipLaunchKernelGGL((bsgs_inner_batch_kernel<16, BSGS_BATCH_CB>), grid, dim3(TPB), 0, G.stream, U, B, P, tab_dev, nj,
+                       gs, lvl, G.logn, cnt, G.dev.mc);
+  else
+    hipLaunchKernelGGL((bsgs_inner_batch_kernel<8, BSGS_BATCH_CB>), grid, dim3(TPB), 0, G.stream, U, B, P, tab_dev, nj,
+                       gs, lvl, G.logn, cnt, G.dev.mc);
+  HIP_CHECK(hipGetLastError());
+}
+
+// out [cnt][2][lvl][n] = base (null: 0) + sum over t < nt of R[t] ([cnt][2][lvl][n]
+// each, r_stride words apart): bsgs_sum_kernel over a whole chunk, total =
+// cnt 2 lvl n words.  out may be base.  grid: (total / 2 / TPB).
+__global__ void __launch_bounds__(TPB) bsgs_sum_batch_kernel(uint64_t *out, const uint64_t *base, const uint64_t *R,
+                                                             unsigned nt, size_t r_stride, size_t total, unsigned lvl,
+                                                             unsigned logn, const ModConst *mc)
+{
+  const size_t w = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 2;
+  if (w >= total)
+    return;
+  const uint64_t q = mc[(unsigned)((w >> logn) % lvl)].q;
+  bsgs_u2 s{0, 0};
+  if (base)
+    s = *(const bsgs_u2 *)(base + w);
+  for (unsigned t = 0; t < nt; t++) {
+    const bsgs_u2 r = *(const bsgs_u2 *)(R + t * r_stride + w);
+    s = bsgs_u2{add_mod(s.x, r.x, q), add_mod(s.y, r.y, q)};
+  }
+  *(bsgs_u2 *)(out + w) = s;
+}
+
+void k_bsgs_sum_batch(uint64_t *out, const uint64_t *base, const uint64_t *R, unsigned nt, size_t r_stride,
+                      unsigned lvl, unsigned cnt)
+{
+  const size_t total = (size_t)cnt * 2 * lvl << G.logn, blocks = (total / 2 + TPB - 1) / TPB;
+  if (!cnt || blocks > 0x7fffffffu)
+    gpqhe_die("k_bsgs_sum_batch: %u ciphertexts in one chunk", cnt);
+  ProfScope ps(KC_BSGS_SUM_BATCH, 8.0 * total * (nt + (base ? 2 : 1)));
+  hipLaunchKernelGGL(bsgs_sum_batch_kernel, dim3((unsigned)blocks), dim3(TPB), 0, G.stream, out, base, R, nt, r_stride,
+                     total, lvl, G.logn, G.dev.mc);
   HIP_CHECK(hipGetLastError());
 }

@@ -476,7 +476,7 @@ enum KClass {
   KC_KS_ROWS, KC_DN_COLS, KC_DN_ROWS, KC_D2_ROWS, KC_NTT2_COLS_FWD, KC_NTT3_ROWS_FWD, KC_NTT3_ROWS_INV,
   KC_NTT2_COLS_INV, KC_KS_COLS4, KC_NTT_SMALL_FWD, KC_NTT_SMALL_INV, KC_GEMV_INNER, KC_KSQ_DROP, KC_KSQ_KEEP,
   KC_MODUP_SMALL, KC_DOWN_SMALL, KC_GEMV_WIN, KC_GEMV_FBC, KC_GEMV_FOLD, KC_GEMV_C0, KC_BSGS_KS, KC_BSGS_INNER,
-  KC_BSGS_SUM, KC_COUNT
+  KC_BSGS_SUM, KC_BSGS_INNER_BATCH, KC_BSGS_SUM_BATCH, KC_COUNT
 };
 struct ProfScope {
   int cls;
@@ -537,6 +537,13 @@ void k_bsgs_inner(uint64_t *U, const uint64_t *B, const uint64_t *P, const int *
                   unsigned ndiag, unsigned lvl);
 // out [2][lvl][n] <- base (or 0) + R[0] + .. + R[cnt - 1] (r_stride words apart)
 void k_bsgs_sum(uint64_t *out, const uint64_t *base, const uint64_t *R, unsigned cnt, size_t r_stride, unsigned lvl);
+// he_gemv_bsgs_batch: the same two over a chunk of cnt ciphertexts in
+// slot-major buffers, B [gs][cnt][2][lvl][n] -> U [nj][cnt][2][lvl][n], and
+// out [cnt][2][lvl][n] <- base (or 0) + R[0] + .. + R[nt - 1] (r_stride apart)
+void k_bsgs_inner_batch(uint64_t *U, const uint64_t *B, const uint64_t *P, const int *tab_dev, unsigned nj, unsigned gs,
+                        unsigned ndiag, unsigned lvl, unsigned cnt);
+void k_bsgs_sum_batch(uint64_t *out, const uint64_t *base, const uint64_t *R, unsigned nt, size_t r_stride,
+                      unsigned lvl, unsigned cnt);
 void tables_upload();
 void tables_prewarm();
 void tables_free();

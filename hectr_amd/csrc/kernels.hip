@@ -49,7 +49,7 @@ static const char *kc_names[KC_COUNT] = {
   "ntt2_cols_kernel<inv>", "ks_cols4_kernel", "ntt_small_kernel<fwd>", "ntt_small_kernel<inv>",
   "gemv_inner_kernel", "ksq_kernel<drop>", "ksq_kernel<keep>", "modup_small_kernel", "moddown_small_kernel",
   "gemv_win_kernel", "gemv_fbc_kernel", "gemv_fold_kernel", "gemv_c0_kernel", "bsgs_ks_kernel",
-  "bsgs_inner_kernel", "bsgs_sum_kernel"};
+  "bsgs_inner_kernel", "bsgs_sum_kernel", "bsgs_inner_batch_kernel", "bsgs_sum_batch_kernel"};
 
 struct ProfEntry {
   int cls;

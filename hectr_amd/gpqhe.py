@@ -158,6 +158,12 @@ PRODUCT_EXT = {
     "he_gemv_bsgs_default_g": (C.c_uint, []),
 }
 
+#: include/gpqhe_ext_batch.h: batched forms of the extensions, product only,
+#: bound like PRODUCT_EXT
+PRODUCT_EXT_BATCH = {
+    "he_gemv_bsgs_batch": (None, [VP, VP, VP, C.c_size_t, C.c_uint, OBJ, C.c_uint]),
+}
+
 
 def _cplx(z) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(z, dtype=np.complex128))
@@ -179,7 +185,7 @@ class Engine:
             f = getattr(self.lib, sym)
             f.restype = res
             f.argtypes = args
-        for sym, (res, args) in PRODUCT_EXT.items():
+        for sym, (res, args) in {**PRODUCT_EXT, **PRODUCT_EXT_BATCH}.items():
             if hasattr(self.lib, sym):  # not the oracle, nor an older library under GPQHE_LIB
                 f = getattr(self.lib, sym)
                 f.restype = res
@@ -332,6 +338,12 @@ class Engine:
         if not hasattr(self.lib, sym):
             raise AttributeError(f"{self.name} library {self.path} does not export {sym} (include/gpqhe_ext.h)")
         return getattr(self.lib, sym)
+
+    def gemv_bsgs_batch(self, y_ptr, M, x_ptr, count, nlimbs, rk, g=0):
+        """gemv_bsgs over `count` ciphertexts in device memory: x_ptr
+        [count][2][nlimbs][n] -> y_ptr [count][2][nlimbs-1][n] (include/gpqhe_ext_batch.h)."""
+        M = _cplx(M)
+        self._ext("he_gemv_bsgs_batch")(y_ptr, M.ctypes.data, x_ptr, count, nlimbs, rk, g)
 
     def gemv_bsgs(self, y, M, x, rk, g=0):
         """y = M x by baby-step giant-step (g = 0: the default baby-step count)."""
