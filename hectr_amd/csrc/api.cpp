@@ -3717,6 +3717,150 @@ extern "C" void he_gemv_bsgs_batch(uint64_t *y, const gpqhe_complex_t M[], const
   }
 }
 
+// ---------------------------------------------------------------------------
+// he_enc_pk_batch / he_dec_dcd_batch (include/gpqhe_ext_batch.h): the two ends
+// of the batch entry points.  Chunks sized by GPQHE_WS_MIB (GPQHE_CHUNK: the
+// test hook of he_mul_rescale_batch), a fixed number of launches per chunk.
+// ---------------------------------------------------------------------------
+static size_t ntt_group_polys(unsigned nlimbs);
+
+static size_t io_chunk(size_t count, size_t per_ct_words, size_t cap)
+{
+  size_t chunk = std::min(std::max<size_t>(1, bsgs_budget() / per_ct_words), std::max<size_t>(1, cap));
+  if (const char *e = getenv("GPQHE_CHUNK"))
+    chunk = std::max<size_t>(1, std::min<size_t>(chunk, strtoul(e, nullptr, 0)));
+  const size_t nchunks = (count + chunk - 1) / chunk;  // equal chunks, as the other batch calls
+  return (count + nchunks - 1) / nchunks;
+}
+
+// k_ntt over npolys polynomials of nlimbs limbs in poly_ntt_batch's groups
+static void ntt_polys(uint64_t *data, size_t npolys, unsigned nlimbs, bool inverse)
+{
+  const size_t per = ntt_group_polys(nlimbs), w = (size_t)nlimbs * G.n;
+  for (size_t p0 = 0; p0 < npolys; p0 += per)
+    k_ntt(qlimbs(data + p0 * w, nlimbs, (unsigned)std::min(per, npolys - p0), w), inverse);
+}
+
+static void io_check(const char *who, unsigned nlimbs, unsigned slots)
+{
+  if (nlimbs < 1 || nlimbs > G.L)
+    gpqhe_die("%s: bad level %u", who, nlimbs);
+  if (!slots || (slots & (slots - 1)) || slots > G.n / 2)
+    gpqhe_die("%s: bad slot count %u", who, slots);
+}
+
+extern "C" void he_enc_pk_batch(uint64_t *x, const gpqhe_complex_t z[], size_t count, unsigned int slots,
+                                double scale, unsigned int nlimbs, const he_pk_t *pk)
+{
+  HPROF("enc_pk_batch");
+  check_ctx();
+  const unsigned lvl = nlimbs, s = slots;
+  io_check("he_enc_pk_batch", lvl, s);
+  if (!pk || !pk->data || pk->nlimbs < lvl)
+    gpqhe_die("he_enc_pk_batch: no public key at level %u", lvl);
+  if (!count)
+    return;
+  if (!x || !z)
+    gpqhe_die("he_enc_pk_batch: null argument");
+  const size_t n = G.n, w = (size_t)lvl * n;
+  // the streams of count he_enc_pk calls: base + 3 i + {0, 1, 2}
+  const uint64_t base = G.counter;
+  G.counter += 3 * (uint64_t)count;
+  // from gpu_ecd_min() slots the special FFT runs on the GPU (one upload of
+  // the chunk's z, staged: at most 64 MiB of it), below it on the host (one
+  // upload of the chunk's coefficients)
+  const bool gpu = s >= gpu_ecd_min();
+  const size_t per_ct = 3 * w + 2 * (size_t)s * (gpu ? 2 : 1);
+  const size_t chunk = io_chunk(count, per_ct, gpu ? std::min<size_t>(16384, ((size_t)4 << 20) / s) : 16384);
+  Ws ovf(gpu ? 1 : 0);
+  if (gpu)
+    HIP_CHECK(hipMemsetAsync(ovf.p, 0, 8, G.stream));
+  std::vector<int64_t> hv;
+  for (size_t c0 = 0; c0 < count; c0 += chunk) {
+    const unsigned cnt = (unsigned)std::min(chunk, count - c0);
+    Ws vee(3 * cnt * w), coef(2 * (size_t)s * cnt);
+    const double *zc = (const double *)z + 2 * c0 * s;
+    if (gpu) {
+      Ws work(2 * (size_t)s * cnt);
+      upload(work.p, zc, (size_t)cnt * s * 16);
+      k_encode_slots_batch((int64_t *)coef.p, (double *)work.p, (int *)ovf.p, s, scale, cnt);
+    } else {
+      hv.resize(2 * (size_t)s * cnt);
+      for (unsigned i = 0; i < cnt; i++)
+        hm_encode_slots(hv.data() + 2 * (size_t)s * i, zc + 2 * (size_t)s * i, s, scale);
+      upload(coef.p, hv.data(), hv.size() * 8);
+    }
+    k_enc_sample_batch(vee.p, base + 3 * (uint64_t)c0, (const int64_t *)coef.p, s, lvl, cnt);
+    ntt_polys(vee.p, 3 * (size_t)cnt, lvl, false);
+    k_enc_combine_chunk(x + c0 * 2 * w, vee.p, limb(pk, 0, 0), limb(pk, 1, 0), lvl, cnt);
+  }
+  if (gpu) {
+    // the single encode's overflow check, once for the batch
+    int h = 0;
+    HIP_CHECK(hipMemcpyAsync(&h, ovf.p, sizeof(int), hipMemcpyDeviceToHost, G.stream));
+    HIP_CHECK(hipStreamSynchronize(G.stream));
+    if (h)
+      gpqhe_die("encode overflow (|value * scale| >= 2^63)");
+  }
+}
+
+// The folded path (k_dec_fold, k_fold_decode) reads each ciphertext once and
+// transforms 2 slots points per limb; it needs a gap n / 2 slots >= 2 and the
+// one-workgroup decoder.  Otherwise, and under GPQHE_DCD_FOLD=0: c0 + c1 s of
+// the chunk, its inverse transforms, and the single call's decoder per
+// ciphertext.  Same doubles either way.
+extern "C" void he_dec_dcd_batch(gpqhe_complex_t z[], const uint64_t *y, size_t count, unsigned int nlimbs,
+                                 double scale, unsigned int slots, const poly_mpi_t *sk)
+{
+  HPROF("dec_dcd_batch");
+  check_ctx();
+  const unsigned nl = nlimbs, s = slots;
+  io_check("he_dec_dcd_batch", nl, s);
+  if (!sk || !sk->data || sk->nlimbs < nl)
+    gpqhe_die("he_dec_dcd_batch: no secret key at level %u", nl);
+  if (!count)
+    return;
+  if (!y || !z)
+    gpqhe_die("he_dec_dcd_batch: null argument");
+  const size_t n = G.n, w = (size_t)nl * n, zb = (size_t)s * 16;
+  const bool fold = env_u("GPQHE_DCD_FOLD", 1) != 0 && s <= GPQHE_DCD_ONEPASS && 2 * (size_t)s < n;
+  // up to GPQHE_DCD_ONEPASS slots the decoder writes each value once: straight
+  // into pinned host memory (up to 64 MiB of it)
+  const bool pinned = s <= GPQHE_DCD_ONEPASS && count * zb <= ((size_t)64 << 20);
+  Ws zdev(pinned ? 0 : 2 * (size_t)s * count);
+  double *zd = pinned ? (double *)zpin(count * zb) : (double *)zdev.p;
+  const size_t chunk = io_chunk(count, fold ? 4 * (size_t)nl * s : w, 16384);
+  for (size_t c0 = 0; c0 < count; c0 += chunk) {
+    const unsigned cnt = (unsigned)std::min(chunk, count - c0);
+    const uint64_t *yc = y + c0 * 2 * w;
+    double *zc = zd + 2 * c0 * s;
+    if (fold) {
+      const size_t fw = 2 * (size_t)s * nl * cnt;
+      Ws F(fw), D(fw);
+      k_dec_fold(F.p, yc, sk->data, s, nl, cnt);
+      k_fold_decode(zc, D.p, F.p, nl, s, scale, cnt);
+    } else {
+      Ws P(cnt * w);
+      k_dec_batch(P.p, yc, sk->data, nl, cnt);
+      ntt_polys(P.p, cnt, nl, true);
+      for (unsigned i = 0; i < cnt; i++)
+        k_decode(zc + 2 * (size_t)s * i, P.p + i * w, nl, s, scale);
+    }
+  }
+  if (!pinned)
+    HIP_CHECK(hipMemcpyAsync(z, zd, count * zb, hipMemcpyDeviceToHost, G.stream));
+  HIP_CHECK(hipStreamSynchronize(G.stream));
+  if (pinned)
+    memcpy(z, g_zpin, count * zb);
+}
+
+// groups of ~224 MiB (ntt_batch), at most 65535 limbs a launch
+static size_t ntt_group_polys(unsigned nlimbs)
+{
+  static const size_t group_mib = env_u("GPQHE_NTT_GROUP_MIB", 224);
+  return std::max<size_t>(1, std::min<size_t>(65535 / nlimbs, (group_mib << 20) / ((size_t)nlimbs * G.n * 8)));
+}
+
 static void ntt_batch(uint64_t *data, size_t npolys, unsigned nlimbs, bool inverse)
 {
   check_ctx();
@@ -3727,9 +3871,7 @@ static void ntt_batch(uint64_t *data, size_t npolys, unsigned nlimbs, bool inver
   // ms): 96 7.46-7.56, 160 7.20-7.26, 192 6.84-6.92, 224 6.62-6.82, 240
   // 6.76-6.77, 256 6.72-7.04, 320 7.24, 512 7.42, whole batch 7.31-7.34.
   // (GPQHE_NTT_GROUP_MIB: the group size for sweeps)
-  static const size_t group_mib = env_u("GPQHE_NTT_GROUP_MIB", 224);
-  const size_t per = std::max<size_t>(1, std::min<size_t>(65535 / nlimbs, (group_mib << 20) /
-                                                                              ((size_t)nlimbs * G.n * 8)));
+  const size_t per = ntt_group_polys(nlimbs);
   // the inverse walks the groups from the last one (GPQHE_NTT_REV): after a
   // forward batch, its last group's output is what the Infinity Cache holds
   static const bool rev = env_u("GPQHE_NTT_REV", 1) != 0;

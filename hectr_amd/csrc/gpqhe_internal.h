@@ -476,7 +476,8 @@ enum KClass {
   KC_KS_ROWS, KC_DN_COLS, KC_DN_ROWS, KC_D2_ROWS, KC_NTT2_COLS_FWD, KC_NTT3_ROWS_FWD, KC_NTT3_ROWS_INV,
   KC_NTT2_COLS_INV, KC_KS_COLS4, KC_NTT_SMALL_FWD, KC_NTT_SMALL_INV, KC_GEMV_INNER, KC_KSQ_DROP, KC_KSQ_KEEP,
   KC_MODUP_SMALL, KC_DOWN_SMALL, KC_GEMV_WIN, KC_GEMV_FBC, KC_GEMV_FOLD, KC_GEMV_C0, KC_BSGS_KS, KC_BSGS_INNER,
-  KC_BSGS_SUM, KC_BSGS_INNER_BATCH, KC_BSGS_SUM_BATCH, KC_COUNT
+  KC_BSGS_SUM, KC_BSGS_INNER_BATCH, KC_BSGS_SUM_BATCH, KC_FFT_ENC_BATCH, KC_ENC_SAMPLE_BATCH, KC_ENC_COMBINE_BATCH,
+  KC_DEC_FOLD, KC_FOLD_DCD, KC_DEC_BATCH, KC_COUNT
 };
 struct ProfScope {
   int cls;
@@ -544,6 +545,29 @@ void k_bsgs_inner_batch(uint64_t *U, const uint64_t *B, const uint64_t *P, const
                         unsigned ndiag, unsigned lvl, unsigned cnt);
 void k_bsgs_sum_batch(uint64_t *out, const uint64_t *base, const uint64_t *R, unsigned nt, size_t r_stride,
                       unsigned lvl, unsigned cnt);
+// he_enc_pk_batch / he_dec_dcd_batch (api.cpp) over a chunk of cnt ciphertexts.
+// Compact coefficients: 2 s int64 values per ciphertext, value j is
+// coefficient j n / 2s of its encoding (hm_encode_slots).
+// GPU encoder: work [cnt][s] complex values (device, overwritten) -> coef
+// [cnt][2 s], the values of k_encode_coeffs; ovf (device int, cleared by the
+// caller) is set on overflow.  Asynchronous.
+void k_encode_slots_batch(int64_t *coef, double *work, int *ovf, unsigned s, double scale, unsigned cnt);
+// vee [cnt][3][nl][n] <- (v, e0 + m, e1) of ciphertext i from ChaCha streams
+// stream + 3 i + {0, 1, 2} (k_sample_enc's values with its EncCoef rows), m
+// from coef (device)
+void k_enc_sample_batch(uint64_t *vee, uint64_t stream, const int64_t *coef, unsigned s, unsigned nl, unsigned cnt);
+// x [cnt][2][nl][n] <- (v pk0 + e0, v pk1 + e1) of the transformed vee
+void k_enc_combine_chunk(uint64_t *x, const uint64_t *vee, const uint64_t *pk0, const uint64_t *pk1, unsigned nl,
+                         unsigned cnt);
+// F [cnt][nl][2 s] <- the sums of c0 + c1 s over the 2 s contiguous blocks of
+// n / 2s words of every limb of y [cnt][2][nl][n]
+void k_dec_fold(uint64_t *F, const uint64_t *y, const uint64_t *sk, unsigned s, unsigned nl, unsigned cnt);
+// z [cnt][s] complex values <- he_dcd of the 2 s coefficients F folds to: the
+// 2 s-point inverse transform of each limb (into D [cnt][nl][2 s]), then
+// k_decode's lift and FFT on that compact layout.  s <= GPQHE_DCD_ONEPASS.
+void k_fold_decode(double *z, uint64_t *D, const uint64_t *F, unsigned nl, unsigned s, double scale, unsigned cnt);
+// pt [cnt][nl][n] <- c0 + c1 s of y [cnt][2][nl][n]
+void k_dec_batch(uint64_t *pt, const uint64_t *y, const uint64_t *sk, unsigned nl, unsigned cnt);
 void tables_upload();
 void tables_prewarm();
 void tables_free();

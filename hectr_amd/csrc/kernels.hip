@@ -49,7 +49,9 @@ static const char *kc_names[KC_COUNT] = {
   "ntt2_cols_kernel<inv>", "ks_cols4_kernel", "ntt_small_kernel<fwd>", "ntt_small_kernel<inv>",
   "gemv_inner_kernel", "ksq_kernel<drop>", "ksq_kernel<keep>", "modup_small_kernel", "moddown_small_kernel",
   "gemv_win_kernel", "gemv_fbc_kernel", "gemv_fold_kernel", "gemv_c0_kernel", "bsgs_ks_kernel",
-  "bsgs_inner_kernel", "bsgs_sum_kernel", "bsgs_inner_batch_kernel", "bsgs_sum_batch_kernel"};
+  "bsgs_inner_kernel", "bsgs_sum_kernel", "bsgs_inner_batch_kernel", "bsgs_sum_batch_kernel",
+  "fft_enc_batch_kernel", "enc_sample_batch_kernel", "enc_combine_batch_kernel", "dec_fold_kernel",
+  "fold_dcd_kernel", "dec_batch_kernel"};
 
 struct ProfEntry {
   int cls;
@@ -4183,6 +4185,354 @@ void k_fill_uniform(uint64_t *data, size_t npolys, unsigned nlimbs, uint64_t see
                        G.stream, data + p0 * nlimbs * G.n, G.logn, nlimbs, seed, G.dev.mc);
     HIP_CHECK(hipGetLastError());
   }
+}
+
+// ===========================================================================
+// he_enc_pk_batch / he_dec_dcd_batch (include/gpqhe_ext_batch.h): a chunk of
+// ciphertexts per launch.  Every value is the one the single calls' kernels
+// give: integer steps are exact on canonical residues, and the floating-point
+// steps are the encoder's and decoder's own (fft_enc_bfly, dcd_chunk).
+// ===========================================================================
+// The GPU encoder over cnt vectors (blockIdx.y): fft_enc_stage_kernel /
+// fft_enc_lds_kernel on vector blockIdx.y, then the rounding of
+// fft_enc_round_kernel into the compact layout (value j = coefficient j gap).
+__global__ void fft_enc_stage_batch_kernel(double2 *v, unsigned s, unsigned len, const double2 *ksi,
+                                           const unsigned *rot)
+{
+  const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= s / 2)
+    return;
+  v += (size_t)blockIdx.y * s;
+  const unsigned h = len >> 1, lq = len << 2, M = 4 * s;
+  const unsigned i = (t / h) * len, j = t % h;
+  const unsigned idx = (lq - rot[j] % lq) * (M / lq);
+  fft_enc_bfly(v[i + j], v[i + j + h], ksi[idx]);
+}
+
+__global__ void __launch_bounds__(512) fft_enc_lds_batch_kernel(double2 *v, unsigned s, unsigned len0,
+                                                                const double2 *ksi, const unsigned *rot)
+{
+  __shared__ double2 c[FFT_LDS];
+  v += (size_t)blockIdx.y * s;
+  const unsigned base = blockIdx.x * len0, M = 4 * s;
+  for (unsigned e = threadIdx.x; e < len0; e += blockDim.x)
+    c[e] = v[base + e];
+  __syncthreads();
+  for (unsigned len = len0; len >= 2; len >>= 1) {
+    const unsigned h = len >> 1, lq = len << 2;
+    for (unsigned t = threadIdx.x; t < len0 / 2; t += blockDim.x) {
+      const unsigned i = (t / h) * len, j = t % h;
+      const unsigned idx = (lq - rot[j] % lq) * (M / lq);
+      fft_enc_bfly(c[i + j], c[i + j + h], ksi[idx]);
+    }
+    __syncthreads();
+  }
+  for (unsigned e = threadIdx.x; e < len0; e += blockDim.x)
+    v[base + e] = c[e];
+}
+
+__global__ void fft_enc_round_batch_kernel(int64_t *coef, const double2 *v, unsigned s, unsigned logs, double scale,
+                                           int *overflow)
+{
+  const unsigned slot = blockIdx.x * blockDim.x + threadIdx.x;
+  if (slot >= s)
+    return;
+  const size_t c = blockIdx.y;
+  const double2 u = v[c * s + (logs ? __brev(slot) >> (32 - logs) : 0)];
+  const double re = u.x / (double)s * scale, im = u.y / (double)s * scale;
+  if (fabs(re) >= 9.2e18 || fabs(im) >= 9.2e18)
+    *overflow = 1;
+  coef[c * 2 * s + slot] = llround(re);
+  coef[c * 2 * s + s + slot] = llround(im);
+}
+
+void k_encode_slots_batch(int64_t *coef, double *work, int *ovf, unsigned s, double scale, unsigned cnt)
+{
+  const FftDev &T = fft_dev(s);
+  double2 *v = (double2 *)work;
+  ProfScope ps(KC_FFT_ENC_BATCH, 16.0 * s * cnt * (2.0 * __builtin_ctz(s > FFT_LDS ? s / FFT_LDS : 1u) + 3));
+  unsigned len = s;
+  for (; len > FFT_LDS; len >>= 1)
+    hipLaunchKernelGGL(fft_enc_stage_batch_kernel, dim3((s / 2 + TPB - 1) / TPB, cnt), dim3(TPB), 0, G.stream, v, s,
+                       len, T.ksi, T.rot);
+  if (len >= 2)
+    hipLaunchKernelGGL(fft_enc_lds_batch_kernel, dim3(s / len, cnt), dim3(std::min(512u, std::max(64u, len / 2))), 0,
+                       G.stream, v, s, len, T.ksi, T.rot);
+  hipLaunchKernelGGL(fft_enc_round_batch_kernel, dim3((s + TPB - 1) / TPB, cnt), dim3(TPB), 0, G.stream, coef, v, s,
+                     (unsigned)__builtin_ctz(s), scale, ovf);
+  HIP_CHECK(hipGetLastError());
+}
+
+// sample_enc_kernel over a chunk: noise polynomial y = 3 i + {0, 1, 2} of
+// ciphertext i from ChaCha stream `stream + y`, one block per coefficient,
+// lifted to the nl moduli; e0 (y = 3 i + 1) takes the plaintext's coefficient
+// k from the compact device array where k is a multiple of the gap 2^logT.
+__global__ void enc_sample_batch_kernel(uint64_t *vee, unsigned logn, unsigned nl, ChachaKey key, uint64_t stream,
+                                        const int64_t *coef, unsigned logT, unsigned m2, const ModConst *mc)
+{
+  const unsigned k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= (1u << logn))
+    return;
+  const unsigned y = blockIdx.y;
+  const int v = enc_noise_value(key, stream, y, k);
+  const bool addm = y % 3 == 1 && !(k & ((1u << logT) - 1));
+  const int64_t mco = addm ? coef[(size_t)(y / 3) * m2 + (k >> logT)] : 0;
+  uint64_t *dst = vee + (((size_t)y * nl) << logn) + k;
+  for (unsigned l = 0; l < nl; l++) {
+    const ModConst &m = mc[l];
+    uint64_t r = v >= 0 ? (uint64_t)v : m.q - (uint64_t)(-v);
+    if (addm)
+      r = add_mod(r, lift_i64(mco, m), m.q);
+    dst[(size_t)l << logn] = r;
+  }
+}
+
+void k_enc_sample_batch(uint64_t *vee, uint64_t stream, const int64_t *coef, unsigned s, unsigned nl, unsigned cnt)
+{
+  const unsigned logT = G.logn - 1 - (unsigned)__builtin_ctz(s);
+  ProfScope ps(KC_ENC_SAMPLE_BATCH, 8.0 * G.n * nl * 3 * cnt + 16.0 * s * cnt);
+  hipLaunchKernelGGL(enc_sample_batch_kernel, dim3((G.n + TPB - 1) / TPB, 3 * cnt), dim3(TPB), 0, G.stream, vee,
+                     G.logn, nl, G.key, stream, coef, logT, 2 * s, G.dev.mc);
+  HIP_CHECK(hipGetLastError());
+}
+
+// enc_batch_kernel (m already in e0) into the batch layout: a workgroup holds
+// its public-key words in registers across IOB_CG ciphertexts.
+constexpr unsigned IOB_CG = 8;
+
+__global__ void enc_combine_batch_kernel(uint64_t *x, const uint64_t *vee, const uint64_t *pk0, const uint64_t *pk1,
+                                         unsigned logn, unsigned nl, unsigned cnt, const ModConst *mc)
+{
+  const size_t n = (size_t)1 << logn;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n)
+    return;
+  const ModConst m = mc[blockIdx.y];
+  const size_t o = ((size_t)blockIdx.y << logn) + i, w = (size_t)nl << logn;
+  const uint64_t p0 = pk0[o], p1 = pk1[o];
+  const unsigned c0 = blockIdx.z * IOB_CG, c1 = min(c0 + IOB_CG, cnt);
+  for (unsigned c = c0; c < c1; c++) {
+    const uint64_t *v = vee + 3 * c * w;
+    const uint64_t vv = v[o];
+    x[2 * c * w + o] = add_mod(v[w + o], mul_mod(vv, p0, m), m.q);
+    x[2 * c * w + w + o] = add_mod(v[2 * w + o], mul_mod(vv, p1, m), m.q);
+  }
+}
+
+void k_enc_combine_chunk(uint64_t *x, const uint64_t *vee, const uint64_t *pk0, const uint64_t *pk1, unsigned nl,
+                         unsigned cnt)
+{
+  ProfScope ps(KC_ENC_COMBINE_BATCH, 8.0 * G.n * nl * (5.0 * cnt + 2.0 * ((cnt + IOB_CG - 1) / IOB_CG)));
+  hipLaunchKernelGGL(enc_combine_batch_kernel, dim3((G.n + TPB - 1) / TPB, nl, (cnt + IOB_CG - 1) / IOB_CG),
+                     dim3(TPB), 0, G.stream, x, vee, pk0, pk1, G.logn, nl, cnt, G.dev.mc);
+  HIP_CHECK(hipGetLastError());
+}
+
+// dec_kernel over a chunk, the secret-key word held across IOB_CG ciphertexts.
+__global__ void dec_batch_kernel(uint64_t *pt, const uint64_t *y, const uint64_t *s, unsigned logn, unsigned nl,
+                                 unsigned cnt, const ModConst *mc)
+{
+  const size_t n = (size_t)1 << logn;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n)
+    return;
+  const ModConst m = mc[blockIdx.y];
+  const size_t o = ((size_t)blockIdx.y << logn) + i, w = (size_t)nl << logn;
+  const uint64_t sv = s[o];
+  const unsigned c0 = blockIdx.z * IOB_CG, c1 = min(c0 + IOB_CG, cnt);
+  for (unsigned c = c0; c < c1; c++)
+    pt[c * w + o] = add_mod(y[2 * c * w + o], mul_mod(y[2 * c * w + w + o], sv, m), m.q);
+}
+
+void k_dec_batch(uint64_t *pt, const uint64_t *y, const uint64_t *sk, unsigned nl, unsigned cnt)
+{
+  ProfScope ps(KC_DEC_BATCH, 8.0 * G.n * nl * (3.0 * cnt + (cnt + IOB_CG - 1) / IOB_CG));
+  hipLaunchKernelGGL(dec_batch_kernel, dim3((G.n + TPB - 1) / TPB, nl, (cnt + IOB_CG - 1) / IOB_CG), dim3(TPB), 0,
+                     G.stream, pt, y, sk, G.logn, nl, cnt, G.dev.mc);
+  HIP_CHECK(hipGetLastError());
+}
+
+// The decoder reads the coefficients d[j T], j < m = n / T, of d = INTT(c0 +
+// c1 s).  In the NTT order of this engine (word k = a(psi^(2 brev_n(k) + 1)))
+// the first log2 T inverse stages of those coefficients are plain sums over
+// the m contiguous blocks of T words, and the rest is the m-point inverse
+// transform with root psi^T, whose twiddles itw[m' + i] (m' < m) are the
+// first m words of the n-point table (brev_n(j) = T brev_m(j) for j < m).
+//
+// dec_fold_kernel: F[c][l][b] = sum over block b of c0 + c1 s (mod q_l).  A
+// workgroup covers W = max(T, FOLD_TPB) contiguous words of limb l for FOLD_CG
+// ciphertexts (the secret-key word is loaded once for them), every thread
+// summing its words k = base + t + FOLD_TPB i, then a tree over the segments of
+// min(T, FOLD_TPB) threads in LDS.
+constexpr unsigned FOLD_TPB = 256, FOLD_CG = 4;
+
+// c0 + c1 s reduced into [0, q): the exact FP64 product for q < 2^51, the
+// Barrett product above
+template <bool F64> struct FoldMul;
+template <> struct FoldMul<false> {
+  __device__ static __forceinline__ uint64_t dec(uint64_t c0, uint64_t c1, uint64_t sv, const ModConst &m, double,
+                                                 double)
+  {
+    return add_mod(c0, mul_mod(c1, sv, m), m.q);
+  }
+};
+template <> struct FoldMul<true> {
+  // a b mod q for a, b < q < 2^51 (qd = q, qi = fl(1 / q)): h = fl(a b) and
+  // its exact remainder l = a b - h, |l| <= 2^-53 q^2 < q / 4; fl(h qi) is
+  // within 1/2 of h / q < 2^51, so qu lies in [h / q - 3/2, h / q + 1/2] and
+  // h - qu q, an integer below 2^53 in magnitude, comes out of the fma exact;
+  // a b - qu q = that + l lies in (-q, 2 q): one correction each way.
+  __device__ static __forceinline__ uint64_t dec(uint64_t c0, uint64_t c1, uint64_t sv, const ModConst &m, double qd,
+                                                 double qi)
+  {
+    const double a = (double)c1, b = (double)sv;
+    const double h = a * b, l = __builtin_fma(a, b, -h);
+    const double qu = __builtin_floor(h * qi);
+    const double r = __builtin_fma(-qu, qd, h) + l;
+    int64_t t = (int64_t)r;
+    t += t < 0 ? (int64_t)m.q : 0;
+    uint64_t u = (uint64_t)t;
+    u = u >= m.q ? u - m.q : u;
+    return add_mod(c0, u, m.q);
+  }
+};
+
+template <bool F64>
+__global__ void __launch_bounds__(FOLD_TPB) dec_fold_kernel(uint64_t *F, const uint64_t *y, const uint64_t *s,
+                                                            unsigned logn, unsigned nl, unsigned logT, unsigned cnt,
+                                                            unsigned lim0, const ModConst *mcs)
+{
+  __shared__ uint64_t sh[FOLD_CG][FOLD_TPB];
+  const unsigned l = blockIdx.y + lim0, t = threadIdx.x;
+  const unsigned c0 = blockIdx.z * FOLD_CG, nc = min(FOLD_CG, cnt - c0);
+  const ModConst mc = mcs[l];
+  const size_t n = (size_t)1 << logn, w = (size_t)nl << logn;
+  const unsigned T = 1u << logT, W = max(T, FOLD_TPB), seg = min(T, FOLD_TPB);
+  const size_t base = (size_t)blockIdx.x * W;
+  const uint64_t *sl = s + ((size_t)l << logn);
+  const double qd = (double)mc.q, qi = 1.0 / qd;
+  uint64_t acc[FOLD_CG];
+#pragma unroll
+  for (unsigned c = 0; c < FOLD_CG; c++)
+    acc[c] = 0;
+  for (unsigned i = t; i < W; i += FOLD_TPB) {
+    const size_t k = base + i;
+    if (k >= n)
+      break;
+    const uint64_t sv = sl[k];
+#pragma unroll
+    for (unsigned c = 0; c < FOLD_CG; c++)
+      if (c < nc) {
+        const uint64_t *yc = y + 2 * (size_t)(c0 + c) * w + ((size_t)l << logn) + k;
+        acc[c] = add_mod(acc[c], FoldMul<F64>::dec(yc[0], yc[w], sv, mc, qd, qi), mc.q);
+      }
+  }
+#pragma unroll
+  for (unsigned c = 0; c < FOLD_CG; c++)
+    sh[c][t] = acc[c];
+  __syncthreads();
+  for (unsigned h = seg >> 1; h; h >>= 1) {
+    if ((t & (seg - 1)) < h)
+#pragma unroll
+      for (unsigned c = 0; c < FOLD_CG; c++)
+        sh[c][t] = add_mod(sh[c][t], sh[c][t + h], mc.q);
+    __syncthreads();
+  }
+  if (!(t & (seg - 1)) && base + t < n) {
+    const size_t b = (base + t) >> logT, m = n >> logT;
+    for (unsigned c = 0; c < nc; c++)
+      F[((size_t)(c0 + c) * nl + l) * m + b] = sh[c][t];
+  }
+}
+
+void k_dec_fold(uint64_t *F, const uint64_t *y, const uint64_t *sk, unsigned s, unsigned nl, unsigned cnt)
+{
+  const unsigned logT = G.logn - 1 - (unsigned)__builtin_ctz(s), T = 1u << logT;
+  const unsigned W = std::max(T, FOLD_TPB), gx = (G.n + W - 1) / W, gz = (cnt + FOLD_CG - 1) / FOLD_CG;
+  ProfScope ps(KC_DEC_FOLD, 8.0 * G.n * nl * (2.0 * cnt + gz) + 16.0 * s * nl * cnt);
+  // runs of limbs on one arithmetic: the FP64 product below 2^51
+  for (unsigned l0 = 0; l0 < nl;) {
+    const bool f64 = G.q[l0] < (1ull << 51);
+    unsigned l1 = l0 + 1;
+    while (l1 < nl && (G.q[l1] < (1ull << 51)) == f64)
+      l1++;
+    const dim3 grid(gx, l1 - l0, gz);
+    if (f64)
+      hipLaunchKernelGGL(dec_fold_kernel<true>, grid, dim3(FOLD_TPB), 0, G.stream, F, y, sk, G.logn, nl, logT, cnt, l0,
+                         G.dev.mc);
+    else
+      hipLaunchKernelGGL(dec_fold_kernel<false>, grid, dim3(FOLD_TPB), 0, G.stream, F, y, sk, G.logn, nl, logT, cnt,
+                         l0, G.dev.mc);
+    l0 = l1;
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+// fold_dcd_kernel: a workgroup per ciphertext.  Per limb, F into LDS, the m =
+// 2 s-point inverse transform (Gentleman-Sande, the stages of the n-point
+// inverse that are left), n^-1, out to D; then dcd_chunk on D as a ring of
+// m coefficients (gap 1), which the workgroup reads after a barrier as
+// inv_dcd_kernel does.
+template <int NLM>
+__global__ void __launch_bounds__(512) fold_dcd_kernel(double2 *z, uint64_t *D, const uint64_t *F, unsigned nl,
+                                                        unsigned logm, unsigned s, unsigned logs, double scale,
+                                                        const uint64_t *itw, const uint64_t *itwp, unsigned logn,
+                                                        const ModConst *mcs, const uint64_t *ginv, unsigned ld,
+                                                        const double2 *ksi, const unsigned *rot)
+{
+  __shared__ __attribute__((aligned(16))) uint64_t lds[2 * FFT_LDS];
+  const unsigned m = 1u << logm;
+  const uint64_t *Fc = F + (size_t)blockIdx.x * nl * m;
+  uint64_t *Dc = D + (size_t)blockIdx.x * nl * m;
+  for (unsigned l = 0; l < nl; l++) {
+    __syncthreads();  // the previous limb's LDS use
+    const ModConst mc = mcs[l];
+    const uint64_t *w = itw + ((size_t)l << logn), *wp = itwp + ((size_t)l << logn);
+    for (unsigned e = threadIdx.x; e < m; e += blockDim.x)
+      lds[e] = Fc[(size_t)l * m + e];
+    __syncthreads();
+    for (unsigned mm = m >> 1; mm; mm >>= 1) {
+      const unsigned t = m / (2 * mm);
+      for (unsigned b = threadIdx.x; b < m / 2; b += blockDim.x) {
+        const unsigned i = b / t, j = 2 * i * t + b % t;
+        const uint64_t U = lds[j], V = lds[j + t];
+        lds[j] = add_mod(U, V, mc.q);
+        lds[j + t] = mul_shoup(sub_mod(U, V, mc.q), w[mm + i], wp[mm + i], mc.q);
+      }
+      __syncthreads();
+    }
+    for (unsigned e = threadIdx.x; e < m; e += blockDim.x)
+      Dc[(size_t)l * m + e] = mul_shoup(lds[e], mc.ninv, mc.ninvp, mc.q);
+  }
+  __syncthreads();
+  dcd_chunk<NLM>((double2 *)lds, z + (size_t)blockIdx.x * s, 0, Dc, nl, logm, s, logs, s, scale, mcs, ginv, ld, ksi,
+                 rot);
+}
+
+void k_fold_decode(double *z, uint64_t *D, const uint64_t *F, unsigned nl, unsigned s, double scale, unsigned cnt)
+{
+  const FftDev &T = fft_dev(s);
+  if (nl < 1 || nl > G.L || s > FFT_LDS || 2 * s >= G.n)
+    gpqhe_die("k_fold_decode: n = %u, %u limbs, %u slots", G.n, nl, s);
+  garner_table();
+  const unsigned logs = (unsigned)__builtin_ctz(s);
+  const dim3 grid(cnt), block(std::min(512u, std::max(64u, s)));
+  ProfScope ps(KC_FOLD_DCD, (32.0 * nl + 16.0) * s * cnt);
+#define GPQHE_FDCD(NLM)                                                                                       \
+  hipLaunchKernelGGL(fold_dcd_kernel<NLM>, grid, block, 0, G.stream, (double2 *)z, D, F, nl, logs + 1, s, logs, \
+                     scale, G.dev.itw, G.dev.itwp, G.logn, G.dev.mc, g_ginv, G.L, T.ksi, T.rot)
+  if (nl <= 2)
+    GPQHE_FDCD(2);
+  else if (nl <= 4)
+    GPQHE_FDCD(4);
+  else if (nl <= 8)
+    GPQHE_FDCD(8);
+  else if (nl <= 16)
+    GPQHE_FDCD(16);
+  else
+    GPQHE_FDCD(GPQHE_MAXMOD);
+#undef GPQHE_FDCD
+  HIP_CHECK(hipGetLastError());
 }
 
 // ===========================================================================

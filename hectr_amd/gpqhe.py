@@ -164,6 +164,13 @@ PRODUCT_EXT_BATCH = {
     "he_gemv_bsgs_batch": (None, [VP, VP, VP, C.c_size_t, C.c_uint, OBJ, C.c_uint]),
 }
 
+#: include/gpqhe_ext_io_batch.h (part of gpqhe_ext_batch.h): the batch
+#: encryption and decode ends, product only, bound like PRODUCT_EXT
+PRODUCT_EXT_IO_BATCH = {
+    "he_enc_pk_batch": (None, [VP, VP, C.c_size_t, C.c_uint, C.c_double, C.c_uint, OBJ]),
+    "he_dec_dcd_batch": (None, [VP, VP, C.c_size_t, C.c_uint, C.c_double, C.c_uint, OBJ]),
+}
+
 
 def _cplx(z) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(z, dtype=np.complex128))
@@ -185,7 +192,7 @@ class Engine:
             f = getattr(self.lib, sym)
             f.restype = res
             f.argtypes = args
-        for sym, (res, args) in {**PRODUCT_EXT, **PRODUCT_EXT_BATCH}.items():
+        for sym, (res, args) in {**PRODUCT_EXT, **PRODUCT_EXT_BATCH, **PRODUCT_EXT_IO_BATCH}.items():
             if hasattr(self.lib, sym):  # not the oracle, nor an older library under GPQHE_LIB
                 f = getattr(self.lib, sym)
                 f.restype = res
@@ -344,6 +351,19 @@ class Engine:
         [count][2][nlimbs][n] -> y_ptr [count][2][nlimbs-1][n] (include/gpqhe_ext_batch.h)."""
         M = _cplx(M)
         self._ext("he_gemv_bsgs_batch")(y_ptr, M.ctypes.data, x_ptr, count, nlimbs, rk, g)
+
+    def enc_pk_batch(self, x_ptr, zs, pk, slots, scale, nlimbs):
+        """he_ecd_ex + he_enc_pk of the rows of zs [count][slots] into device
+        memory x_ptr [count][2][nlimbs][n] (include/gpqhe_ext_batch.h)."""
+        zs = _cplx(zs).reshape(-1, slots)
+        self._ext("he_enc_pk_batch")(x_ptr, zs.ctypes.data, zs.shape[0], slots, scale, nlimbs, C.byref(pk))
+
+    def dec_dcd_batch(self, y_ptr, count, nlimbs, scale, sk, slots):
+        """he_dec + he_dcd_ex of `count` ciphertexts in device memory y_ptr
+        [count][2][nlimbs][n]: a complex128 array [count][slots]."""
+        z = np.zeros((count, slots), dtype=np.complex128)
+        self._ext("he_dec_dcd_batch")(z.ctypes.data, y_ptr, count, nlimbs, scale, slots, C.byref(sk))
+        return z
 
     def gemv_bsgs(self, y, M, x, rk, g=0):
         """y = M x by baby-step giant-step (g = 0: the default baby-step count)."""

@@ -1,5 +1,6 @@
 """FETCH_SIZE / WRITE_SIZE calibration per access pattern: every kernel of
-scripts/ubench_mem.hip reads 1 GiB and writes 1 GiB per launch.
+scripts/ubench_mem.hip reads 1 GiB and writes 1 GiB per launch (read8 writes
+16 MiB: its WRITE ratio reads 1/64).
 
     python scripts/fetch_calib.py gpurun_out/<run>   (dirs fcal_fetch, fcal_write)
 

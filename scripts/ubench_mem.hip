@@ -12,6 +12,16 @@ __global__ void copy8(uint64_t *o, const uint64_t *x, size_t n)
   for (; i < n; i += (size_t)gridDim.x * 256)
     o[i] = x[i] + 1;
 }
+// plain read: every word of x once, one word written per thread (the rate a
+// kernel that only reads, such as dec_fold_kernel, can be held against)
+__global__ void read8(uint64_t *o, const uint64_t *x, size_t n)
+{
+  size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  uint64_t acc = 0;
+  for (; i < n; i += (size_t)gridDim.x * 256)
+    acc += x[i];
+  o[(size_t)blockIdx.x * 256 + threadIdx.x] = acc;
+}
 __global__ void copy16(ulonglong2 *o, const ulonglong2 *x, size_t n2)
 {
   size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -109,8 +119,8 @@ __global__ void tile16(ulonglong2 *o, const ulonglong2 *x)
   }
 }
 
-// Every kernel reads the 1 GiB buffer x once and writes the 1 GiB buffer o
-// once per launch, so a rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE pass over this
+// Every kernel reads the 1 GiB buffer x once and (all but read8, which writes
+// 16 MiB) writes the 1 GiB buffer o once per launch, so a rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE pass over this
 // binary calibrates the counters per access pattern (scripts/fetch_calib.py).
 int main()
 {
@@ -122,7 +132,7 @@ int main()
   hipEvent_t a, b;
   hipEventCreate(&a);
   hipEventCreate(&b);
-  auto run = [&](const char *name, auto launch) {
+  auto run = [&](const char *name, auto launch, double passes = 2.0) {
     launch();
     hipDeviceSynchronize();
     hipEventRecord(a);
@@ -132,9 +142,10 @@ int main()
     hipEventSynchronize(b);
     float ms;
     hipEventElapsedTime(&ms, a, b);
-    printf("%-8s %7.1f GB/s\n", name, 2.0 * n * 8 * 10 / (ms * 1e6));
+    printf("%-8s %7.1f GB/s\n", name, passes * n * 8 * 10 / (ms * 1e6));
   };
   run("copy8", [&] { hipLaunchKernelGGL(copy8, dim3(8192), dim3(256), 0, 0, o, x, n); });
+  run("read8", [&] { hipLaunchKernelGGL(read8, dim3(8192), dim3(256), 0, 0, o, x, n); }, 1.0);
   run("copy16", [&] { hipLaunchKernelGGL(copy16, dim3(8192), dim3(256), 0, 0, (ulonglong2 *)o, (const ulonglong2 *)x, n / 2); });
   run("tile8", [&] { hipLaunchKernelGGL(tile8, dim3(n / 4096), dim3(256), 0, 0, o, x); });
   run("tile16", [&] { hipLaunchKernelGGL(tile16, dim3(n / 4096), dim3(256), 0, 0, (ulonglong2 *)o, (const ulonglong2 *)x); });
