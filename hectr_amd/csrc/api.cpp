@@ -4,7 +4,7 @@
 // reference src/ctr.c:445-618 and src/hempc.c:216-274 (see gpqhe.h).
 #include "gpqhe_internal.h"
 #include "../../include/gpqhe_ext.h"
-#include "../../include/gpqhe_ext_batch.h"
+#include "../../include/gpqhe_ext_batch.h"  // (and gpqhe_ext_io_batch.h, gpqhe_ext_step_batch.h)
 
 #include <math.h>
 #include <stdio.h>
@@ -13,6 +13,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <iterator>
 #include <list>
 #include <map>
 #include <memory>
@@ -37,6 +38,7 @@ static void fold_cache_trim();
 static unsigned env_u(const char *name, unsigned dflt);
 void gemv_cache_clear();
 static void bsgs_cache_clear();
+static void bsgs2_cache_clear();
 
 void *pool_alloc(size_t bytes)
 {
@@ -1127,6 +1129,7 @@ extern "C" void hectx_exit(void)
   k_prof_release();
   gemv_cache_clear();
   bsgs_cache_clear();
+  bsgs2_cache_clear();
   fold_cache_clear();
   g_key_gen++;
   tables_free();
@@ -3093,9 +3096,9 @@ static BsgsKeys bsgs_find_keys(const BsgsPlan &plan, const he_evk_t rk[], unsign
   BsgsKeys k;
   k.nbs = (unsigned)plan.baby.size();
   k.nj = (unsigned)plan.giant.size();
-  k.has0 = plan.baby[0] == 0;
+  k.has0 = k.nbs && plan.baby[0] == 0;
   k.nbr = k.nbs - k.has0;
-  k.hasj0 = plan.giant[0] == 0;
+  k.hasj0 = k.nj && plan.giant[0] == 0;
   k.njr = k.nj - k.hasj0;
   k.brot.resize(k.nbr);
   k.bkey.resize(k.nbr);
@@ -3137,7 +3140,7 @@ static void bsgs_baby(uint64_t *B, size_t stride, const he_ct_t *x, const BsgsKe
 {
   const unsigned nm = lvl + G.K, ndig = (lvl + G.alpha - 1) / G.alpha;
   const size_t n = G.n, pw = (size_t)lvl * n, accw = 2 * (size_t)nm * n, dw = (size_t)ndig * nm * n;
-  if (k.has0)
+  if (k.has0 && B != x->data)  // (he_hempc_step_batch forms x in slot 0)
     for (unsigned p = 0; p < 2; p++)
       HIP_CHECK(hipMemcpyAsync(B + p * pw, limb(x, p, 0), pw * 8, hipMemcpyDeviceToDevice, G.stream));
   if (!k.nbr)
@@ -3715,6 +3718,285 @@ extern "C" void he_gemv_bsgs_batch(uint64_t *y, const gpqhe_complex_t M[], const
     const unsigned cnt = (unsigned)std::min(chunk, count - c0);
     bsgs_batch_chunk(y + c0 * out_words, x + c0 * in_words, cnt, lvl, *plan, k, rk, budget);
   }
+}
+
+// ---------------------------------------------------------------------------
+// he_gemv2_bsgs_batch / he_hempc_step_batch (include/gpqhe_ext_step_batch.h):
+// y = Ma xa + Mb xb by one BSGS over both operands, and ctr_hempc around it.
+// The two products are summed before the giant rotations, so the inner sums
+// run over the concatenated baby slots of both operands and every giant step
+// of the union is rotated once: 2 (g - 1) + (G - 1) key switches and one
+// rescale per ciphertext.  The stages are he_gemv_bsgs_batch's (same kernels,
+// same slot-major buffers); the step adds step_diff_batch_kernel in front and
+// step_tail_batch_kernel behind (step_batch.hip).
+//
+// The pair plan: one cache entry per (Ma, Mb, level, g), the ordered pair, in
+// a list of its own with bsgs_plan_get's rules -- one lookup per call before
+// the first launch, every eviction there, the entry owns its blocks, bounded by
+// diag_cache_cap(), a larger plan lives in the call's holder, hectx_exit
+// empties it.  It shares nothing with g_bsgs: what he_gemv_bsgs and
+// he_gemv_bsgs_batch look up does not change.
+// ---------------------------------------------------------------------------
+struct Bsgs2Plan {
+  std::vector<double> Ma, Mb;   // the matrices it was made from (compared in place on a lookup)
+  unsigned s = 0, lvl = 0, g = 0;
+  BsgsPlan a, b;                // each operand's diagonals, baby list and giant steps (host lists only)
+  std::vector<unsigned> giant;  // the union of their giant steps, ascending: row order of tab and U
+  std::vector<int> tab;         // [giant][baby slots of a | baby slots of b] -> index into pts, -1: none
+  uint64_t *pts = nullptr;      // [a.ds.size() + b.ds.size()][lvl][n]: a's diagonals, then b's
+  int *tab_dev = nullptr;
+  size_t bytes = 0;
+};
+static std::list<Bsgs2Plan> g_bsgs2;
+static size_t g_bsgs2_bytes = 0;
+
+static void bsgs2_cache_clear()
+{
+  for (Bsgs2Plan &p : g_bsgs2) {
+    pool_free(p.pts);
+    pool_free(p.tab_dev);
+  }
+  g_bsgs2.clear();
+  g_bsgs2_bytes = 0;
+}
+
+struct Bsgs2PlanHold {
+  Bsgs2Plan tmp;
+  std::unique_ptr<Ws> pts, tab;
+};
+
+static const Bsgs2Plan *bsgs2_plan_get(Bsgs2PlanHold &h, const double *Ma, const double *Mb, unsigned lvl, unsigned g)
+{
+  const unsigned s = G.slots;
+  const size_t pw = (size_t)lvl * G.n, mwords = 2 * (size_t)s * s;
+  for (auto it = g_bsgs2.begin(); it != g_bsgs2.end(); ++it)
+    if (it->s == s && it->lvl == lvl && it->g == g && !memcmp(it->Ma.data(), Ma, mwords * 8) &&
+        !memcmp(it->Mb.data(), Mb, mwords * 8)) {
+      g_bsgs2.splice(g_bsgs2.begin(), g_bsgs2, it);
+      return &g_bsgs2.front();
+    }
+  Bsgs2Plan &tmp = h.tmp;
+  bsgs_plan(tmp.a, Ma, g);
+  bsgs_plan(tmp.b, Mb, g);
+  const size_t nda = tmp.a.ds.size(), ndiag = nda + tmp.b.ds.size();
+  if (!ndiag)
+    return &tmp;  // both matrices zero: no blocks
+  std::set_union(tmp.a.giant.begin(), tmp.a.giant.end(), tmp.b.giant.begin(), tmp.b.giant.end(),
+                 std::back_inserter(tmp.giant));
+  const size_t na = tmp.a.baby.size(), nb = tmp.b.baby.size(), gs = na + nb;
+  tmp.tab.assign(tmp.giant.size() * gs, -1);
+  for (size_t r = 0, ja = 0, jb = 0; r < tmp.giant.size(); r++) {
+    if (ja < tmp.a.giant.size() && tmp.a.giant[ja] == tmp.giant[r]) {
+      for (size_t i = 0; i < na; i++)
+        tmp.tab[r * gs + i] = tmp.a.tab[ja * na + i];
+      ja++;
+    }
+    if (jb < tmp.b.giant.size() && tmp.b.giant[jb] == tmp.giant[r]) {
+      for (size_t i = 0; i < nb; i++)
+        if (tmp.b.tab[jb * nb + i] >= 0)
+          tmp.tab[r * gs + na + i] = (int)nda + tmp.b.tab[jb * nb + i];
+      jb++;
+    }
+  }
+  const size_t tabw = (tmp.tab.size() * sizeof(int) + 7) / 8;
+  tmp.bytes = ndiag * pw * 8;
+  if (tmp.bytes > diag_cache_cap()) {
+    h.pts.reset(new Ws(ndiag * pw));
+    h.tab.reset(new Ws(tabw));
+    tmp.pts = h.pts->p;
+    tmp.tab_dev = (int *)h.tab->p;
+  } else {
+    while (!g_bsgs2.empty() && g_bsgs2_bytes + tmp.bytes > diag_cache_cap()) {
+      pool_free(g_bsgs2.back().pts);
+      pool_free(g_bsgs2.back().tab_dev);
+      g_bsgs2_bytes -= g_bsgs2.back().bytes;
+      g_bsgs2.pop_back();
+    }
+    tmp.pts = (uint64_t *)pool_alloc(tmp.bytes);
+    tmp.tab_dev = (int *)pool_alloc(tabw * 8);
+  }
+  bsgs_encode(tmp.a, Ma, lvl, g, tmp.pts);
+  bsgs_encode(tmp.b, Mb, lvl, g, tmp.pts + nda * pw);
+  upload(tmp.tab_dev, tmp.tab.data(), tmp.tab.size() * sizeof(int));
+  if (h.pts)
+    return &tmp;
+  tmp.Ma.assign(Ma, Ma + mwords);  // the owned copies: made on a miss only
+  tmp.Mb.assign(Mb, Mb + mwords);
+  tmp.s = s;
+  tmp.lvl = lvl;
+  tmp.g = g;
+  g_bsgs2_bytes += tmp.bytes;
+  g_bsgs2.push_front(std::move(tmp));
+  return &g_bsgs2.front();
+}
+
+// The four inputs of a step (null: he_gemv2_bsgs_batch, whose operands are given).
+struct StepIn {
+  const uint64_t *xhat, *xr, *uhat, *ur;
+};
+
+// Baby stage of one operand over a chunk, as bsgs_batch_chunk's: slot i of B
+// ([k.nbs][cnt][2][lvl][n]) <- rot(x, baby[i]); x may already be slot 0.
+static void bsgs2_baby(uint64_t *B, const uint64_t *x, unsigned cnt, unsigned lvl, const BsgsKeys &k,
+                       const he_evk_t rk[], size_t budget, bool win)
+{
+  const size_t cw = 2 * (size_t)lvl * G.n, sw = (size_t)cnt * cw;
+  if (!k.nbs)
+    return;
+  if (win) {
+    if (k.has0 && B != x)
+      HIP_CHECK(hipMemcpyAsync(B, x, sw * 8, hipMemcpyDeviceToDevice, G.stream));
+    for (unsigned r = 0; r < k.nbr; r++) {
+      const RotFold &f = bsgs_rot_fold(k.brot[r], lvl, rk);
+      RotFoldUse use(f);
+      k_gemv_batch(B + (size_t)(k.has0 + r) * sw, x, cnt, lvl, f.K, &f.rot, 1, 0);
+    }
+    return;
+  }
+  for (unsigned c = 0; c < cnt; c++) {
+    const he_ct_t cx = ct_view(x + c * cw, lvl);
+    bsgs_baby(B + c * cw, sw, &cx, k, lvl, budget);
+  }
+}
+
+// One chunk of cnt ciphertexts: ka / kb the baby rotations of each operand, kg
+// the giant steps of the union.  st: form xa = xhat - xr and xb = uhat - ur
+// first (into slot 0 of the operand's baby slots where its plan uses the
+// unrotated slot, else into a workspace) and finish with y = uhat - y.
+static void bsgs2_chunk(uint64_t *y, const uint64_t *xa, const uint64_t *xb, const StepIn *st, unsigned cnt,
+                        unsigned lvl, const Bsgs2Plan &plan, const BsgsKeys &ka, const BsgsKeys &kb,
+                        const BsgsKeys &kg, const he_evk_t rk[], size_t budget)
+{
+  const unsigned nm = lvl + G.K, ndig = (lvl + G.alpha - 1) / G.alpha;
+  const size_t n = G.n, pw = (size_t)lvl * n, cw = 2 * pw, sw = (size_t)cnt * cw;  // words: ciphertext, slot
+  const bool win = gemv_win_on(lvl);
+  const unsigned nbs = ka.nbs + kb.nbs;
+  // (the rotated giant steps take the baby slots' place: the inner sums are the last to read those)
+  Ws B((size_t)std::max(nbs, kg.njr) * sw), U((size_t)kg.nj * sw);
+  uint64_t *Ba = B.p, *Bb = B.p + (size_t)ka.nbs * sw, *R = B.p;
+
+  Ws Xd(st && !ka.has0 ? sw : 0), Ud(st && !kb.has0 ? sw : 0);
+  if (st) {
+    uint64_t *xd = ka.has0 ? Ba : Xd.p, *ud = kb.has0 ? Bb : Ud.p;
+    k_step_diff_batch(xd, ud, st->xhat, st->xr, st->uhat, st->ur, lvl, cnt);
+    xa = xd;
+    xb = ud;
+  }
+
+  // baby steps of both operands, then the inner sums over all of their slots
+  bsgs2_baby(Ba, xa, cnt, lvl, ka, rk, budget, win);
+  bsgs2_baby(Bb, xb, cnt, lvl, kb, rk, budget, win);
+  k_bsgs_inner_batch(U.p, B.p, plan.pts, plan.tab_dev, kg.nj, nbs, (unsigned)(plan.a.ds.size() + plan.b.ds.size()), lvl,
+                     cnt);
+
+  // giant steps of the union: u_j of the whole chunk rotated by j g into R
+  if (win) {
+    for (unsigned r = 0; r < kg.njr; r++) {
+      const RotFold &f = bsgs_rot_fold(kg.grot[r], lvl, rk);
+      RotFoldUse use(f);
+      k_gemv_batch(R + (size_t)r * sw, U.p + (size_t)(kg.hasj0 + r) * sw, cnt, lvl, f.K, &f.rot, 1, 0);
+    }
+  } else if (kg.njr) {
+    const unsigned cg = bsgs_giant_chunk(kg, lvl, budget, 0);
+    Ws Dg((size_t)cg * ndig * nm * n), acc((size_t)cg * 2 * nm * n);
+    for (unsigned c = 0; c < cnt; c++)
+      for (unsigned r0 = 0; r0 < kg.njr; r0 += cg)
+        bsgs_giant(R + (size_t)r0 * sw + c * cw, sw, U.p + c * cw, sw, kg, r0, std::min(cg, kg.njr - r0), lvl, Dg.p,
+                   acc.p);
+  }
+
+  // sum over the giant steps, rescale by q_top into y, and the step's tail
+  uint64_t *S = U.p;
+  Ws Sw(kg.njr ? sw : 0);
+  if (kg.njr) {
+    k_bsgs_sum_batch(Sw.p, kg.hasj0 ? U.p : nullptr, R, kg.njr, sw, lvl, cnt);
+    S = Sw.p;
+  }
+  k_moddown(y, (size_t)(lvl - 1) * n, S, pw, 2 * cnt, lvl, 2);
+  if (st)
+    k_step_tail_batch(y, st->uhat, lvl, cnt);
+}
+
+static void bsgs2_run(const char *who, uint64_t *y, const double *Ma, const double *Mb, const uint64_t *xa,
+                      const uint64_t *xb, const StepIn *st, size_t count, unsigned lvl, const he_evk_t rk[],
+                      unsigned g)
+{
+  check_ctx();
+  const unsigned s = G.slots;
+  if (lvl < 2 || lvl > G.L)
+    gpqhe_die("%s: bad level %u", who, lvl);
+  if (!g)
+    g = bsgs_default_g();
+  if (g > s)
+    gpqhe_die("%s: g = %u > slots = %u", who, g, s);
+  const unsigned nm = lvl + G.K, ndig = (lvl + G.alpha - 1) / G.alpha;
+  const size_t n = G.n, pw = (size_t)lvl * n, in_words = 2 * pw, out_words = 2 * (size_t)(lvl - 1) * n;
+  if (!count)
+    return;
+  const uint64_t *ins[4] = {st ? st->xhat : xa, st ? st->xr : xb, st ? st->uhat : nullptr, st ? st->ur : nullptr};
+  for (const uint64_t *x : ins)
+    if (x && y < x + count * in_words && x < y + count * out_words)
+      gpqhe_die("%s: output overlaps an input", who);
+
+  Bsgs2PlanHold hold;
+  const Bsgs2Plan *plan = bsgs2_plan_get(hold, Ma, Mb, lvl, g);
+  if (plan->giant.empty()) {  // both matrices zero: y = 0, up = the lower limbs of uhat
+    HIP_CHECK(hipMemsetAsync(y, 0, count * out_words * 8, G.stream));
+    for (size_t c0 = 0; st && c0 < count; c0 += 16384) {
+      const unsigned cnt = (unsigned)std::min<size_t>(16384, count - c0);
+      k_step_tail_batch(y + c0 * out_words, st->uhat + c0 * in_words, lvl, cnt);
+    }
+    return;
+  }
+  BsgsPlan t;  // every key is found before anything is launched
+  t.baby = plan->a.baby;
+  const BsgsKeys ka = bsgs_find_keys(t, rk, g);
+  t.baby = plan->b.baby;
+  const BsgsKeys kb = bsgs_find_keys(t, rk, g);
+  t.baby.clear();
+  t.giant = plan->giant;
+  const BsgsKeys kg = bsgs_find_keys(t, rk, g);
+
+  // a ciphertext's share of a chunk, in words of one ciphertext (2 lvl n):
+  //   max(nbs_a + nbs_b, njr)  the baby slots of both operands, later the rotated giant steps
+  //   + nj + 1                 the giant steps of the union and the sum
+  //   + 1 per operand of a step whose difference has no slot 0 to live in;
+  // on the windowed path k_gemv_batch's workspace besides (the generic stages'
+  // workspaces do not grow with the chunk)
+  const size_t budget = bsgs_budget();
+  const size_t slots_ct = std::max(ka.nbs + kb.nbs, kg.njr) + kg.nj + 1 + (st ? !ka.has0 + !kb.has0 : 0);
+  const size_t per_ct =
+    slots_ct * 2 * pw + (gemv_win_on(lvl) ? ((size_t)lvl + (size_t)ndig * nm + 2 * (size_t)nm) * n : 0);
+  size_t chunk = std::min<size_t>(std::max<size_t>(1, budget / per_ct), 16384);
+  if (const char *e = getenv("GPQHE_BSGS_CHUNK"))  // test hook: several chunks on a small batch
+    chunk = std::max<size_t>(1, std::min<size_t>(chunk, strtoul(e, nullptr, 0)));
+  else  // equal chunks, as he_gemv_bsgs_batch
+    chunk = (count + (count + chunk - 1) / chunk - 1) / ((count + chunk - 1) / chunk);
+  for (size_t c0 = 0; c0 < count; c0 += chunk) {
+    const unsigned cnt = (unsigned)std::min(chunk, count - c0);
+    const size_t o = c0 * in_words;
+    const StepIn sc = st ? StepIn{st->xhat + o, st->xr + o, st->uhat + o, st->ur + o} : StepIn{};
+    bsgs2_chunk(y + c0 * out_words, st ? nullptr : xa + o, st ? nullptr : xb + o, st ? &sc : nullptr, cnt, lvl, *plan,
+                ka, kb, kg, rk, budget);
+  }
+}
+
+extern "C" void he_gemv2_bsgs_batch(uint64_t *y, const gpqhe_complex_t Ma[], const uint64_t *xa,
+                                    const gpqhe_complex_t Mb[], const uint64_t *xb, size_t count, unsigned int nlimbs,
+                                    const he_evk_t rk[], unsigned int g)
+{
+  HPROF("gemv2_bsgs_batch");
+  bsgs2_run("he_gemv2_bsgs_batch", y, (const double *)Ma, (const double *)Mb, xa, xb, nullptr, count, nlimbs, rk, g);
+}
+
+extern "C" void he_hempc_step_batch(uint64_t *up, const gpqhe_complex_t Ma[], const gpqhe_complex_t Mb[],
+                                    const uint64_t *xhat, const uint64_t *xr, const uint64_t *uhat, const uint64_t *ur,
+                                    size_t count, unsigned int nlimbs, const he_evk_t rk[], unsigned int g)
+{
+  HPROF("hempc_step_batch");
+  const StepIn st{xhat, xr, uhat, ur};
+  bsgs2_run("he_hempc_step_batch", up, (const double *)Ma, (const double *)Mb, nullptr, nullptr, &st, count, nlimbs, rk,
+            g);
 }
 
 // ---------------------------------------------------------------------------

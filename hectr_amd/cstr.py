@@ -311,6 +311,55 @@ def _clz32(v):
     return 32 - int(v).bit_length()
 
 
+def simulate_batch(problems, regulator, on_step=None):
+    """CstrProblem.simulate for several problems in lockstep (they differ, for
+    example, in their disturbance p; all share N and the dimensions):
+    regulator(xhat, uhat, xr, ur) takes [count][.] arrays, one row a problem,
+    and returns u [count][nu].  Every problem's own arithmetic is simulate's,
+    operation for operation.  Returns x [count][N + 1][nx], u [count][N][nu]."""
+    P = len(problems)
+    p0 = problems[0]
+    nx, nu, nd, N = p0.nx, p0.nu, p0.nd, p0.N
+    assert all((pb.nx, pb.nu, pb.nd, pb.N) == (nx, nu, nd, N) for pb in problems)
+    x = np.zeros((P, N + 1, nx))
+    u = np.zeros((P, N, nu))
+    xhatm = np.zeros((P, nx))
+    dhatm = np.zeros((P, nd))
+    rsp = np.zeros(nu)
+    xhat, dhat = np.zeros((P, nx)), np.zeros((P, nd))
+    xr, ur, uhat = np.zeros((P, nx)), np.zeros((P, nu)), np.zeros((P, nu))
+    for k in range(N + 1):
+        for i, pb in enumerate(problems):
+            y = pb.C.sum(axis=1) * x[i, k]                   # ctr_measure quirk
+            e = y - pb.C @ xhatm[i] - pb.Cd @ dhatm[i]       # ctr_measure_forward
+            xhat[i] = xhatm[i] + pb.Lx @ e
+            dhat[i] = dhatm[i] + pb.Ld @ e
+        if k == N:
+            break
+        for i, pb in enumerate(problems):
+            pack = np.concatenate([pb.Bd @ dhat[i], rsp - pb.Hr @ (pb.Cd @ dhat[i])])
+            r = pb.Ginv @ pack                               # ctr_select
+            xr[i], ur[i] = r[:nx], r[nx:]
+            if k == 0:
+                u[i, 0] = ur[i]
+            uhat[i] = u[i, 0] if k == 0 else u[i, k - 1]
+        u[:, k] = regulator(xhat.copy(), uhat.copy(), xr.copy(), ur.copy())
+        if on_step:
+            on_step(k, xhat.copy(), uhat.copy(), xr.copy(), ur.copy(), u[:, k].copy())
+        for i, pb in enumerate(problems):
+            xx = x[i, k] + pb.xs                             # ctr_actuate
+            uu = u[i, k] + pb.us
+            pp = np.array([pb.p[k]]) + pb.ps
+            for _ in range(2):
+                xx = ode15s(xx, uu, pp, pb.dt / 2)
+            x[i, k + 1] = xx - pb.xs
+            xhatm[i] = pb.A @ xhat[i] + pb.B @ u[i, k] + pb.Bd @ dhat[i]   # ctr_estimate
+            dhatm[i] = dhat[i]
+    xs = np.stack([pb.xs for pb in problems])[:, None, :]
+    us = np.stack([pb.us for pb in problems])[:, None, :]
+    return x + xs, u + us
+
+
 class EncryptedRegulator:
     """hectr_enc_states -> ctr_hempc -> hectr_dec_state (src/ctr.c:445-498,
     src/hempc.c:216-274), issuing the same he_* calls in the same order."""
@@ -377,3 +426,57 @@ class EncryptedRegulator:
         e.free(self.pk)
         e.free(self.sk)
         e.free_evks(self.rk)
+
+
+class BatchedEncryptedRegulator:
+    """ctr_hempc for `count` control loops at once through the three batch
+    calls: one he_enc_pk_batch of the 4 count vectors (into one device array
+    sliced four ways), he_hempc_step_batch, he_dec_dcd_batch.  The loops share
+    the problem's gain matrices, the key pair and the he_genrk_bsgs(g) rotation
+    keys.  Device memory comes from torch."""
+
+    def __init__(self, engine, problem: CstrProblem, count, g=0, seed=None, logn=12, logq=109, log_delta=50,
+                 init=True):
+        import torch
+        self.e, self.pb, self.count, self.g = engine, problem, count, g
+        if init:
+            engine.init(logn, logq, problem.slots, log_delta)
+        if seed is not None:
+            engine.set_seed(seed)
+        s = problem.slots
+        self.pk, self.sk = engine.pk(), engine.sk()
+        self.rk = engine.evks(s)
+        engine.keypair(self.pk, self.sk)
+        engine.genrk_bsgs(self.rk, self.sk, g)
+        self.lvl, self.scale = engine.L, engine.info.delta
+        self.cw = 2 * self.lvl * engine.n                  # words of one input ciphertext
+        self.x = torch.zeros(4 * count * self.cw, dtype=torch.int64, device="cuda")
+        self.up = torch.zeros(count * 2 * (self.lvl - 1) * engine.n, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        self.MAz = d2z_matrix(problem.MA, s).ravel()
+        self.MBz = d2z_matrix(problem.MB, s).ravel()
+        self.timings = []
+
+    def __call__(self, xhat, uhat, xr, ur):
+        e, s, cnt = self.e, self.pb.slots, self.count
+        t0 = time.perf_counter()
+        zs = np.zeros((4, cnt, s), dtype=np.complex128)
+        for b, v in enumerate((xhat, xr, uhat, ur)):
+            v = np.asarray(v, dtype=np.float64).reshape(cnt, -1)
+            zs[b, :, :v.shape[1]] = v
+        e.enc_pk_batch(self.x.data_ptr(), zs.reshape(4 * cnt, s), self.pk, s, self.scale, self.lvl)
+        part = [self.x.data_ptr() + 8 * b * cnt * self.cw for b in range(4)]
+        e.hempc_step_batch(self.up.data_ptr(), self.MAz, self.MBz, part[0], part[1], part[2], part[3], cnt, self.lvl,
+                           self.rk, self.g)
+        uz = e.dec_dcd_batch(self.up.data_ptr(), cnt, self.lvl - 1, self.scale, self.sk, s)
+        assert np.all(uz.imag < HECTR_SMALL), "imaginary part too large (src/ctr.c:493-494)"
+        self.timings.append(time.perf_counter() - t0)
+        return uz.real[:, :self.pb.nu].copy()
+
+    def close(self):
+        e = self.e
+        e.sync()
+        e.free(self.pk)
+        e.free(self.sk)
+        e.free_evks(self.rk)
+        self.x = self.up = None

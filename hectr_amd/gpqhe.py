@@ -171,6 +171,13 @@ PRODUCT_EXT_IO_BATCH = {
     "he_dec_dcd_batch": (None, [VP, VP, C.c_size_t, C.c_uint, C.c_double, C.c_uint, OBJ]),
 }
 
+#: include/gpqhe_ext_step_batch.h (part of gpqhe_ext_batch.h): HECTR's
+#: encrypted step over a ciphertext batch, product only, bound like PRODUCT_EXT
+PRODUCT_EXT_STEP_BATCH = {
+    "he_gemv2_bsgs_batch": (None, [VP, VP, VP, VP, VP, C.c_size_t, C.c_uint, OBJ, C.c_uint]),
+    "he_hempc_step_batch": (None, [VP, VP, VP, VP, VP, VP, VP, C.c_size_t, C.c_uint, OBJ, C.c_uint]),
+}
+
 
 def _cplx(z) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(z, dtype=np.complex128))
@@ -192,7 +199,8 @@ class Engine:
             f = getattr(self.lib, sym)
             f.restype = res
             f.argtypes = args
-        for sym, (res, args) in {**PRODUCT_EXT, **PRODUCT_EXT_BATCH, **PRODUCT_EXT_IO_BATCH}.items():
+        for sym, (res, args) in {**PRODUCT_EXT, **PRODUCT_EXT_BATCH, **PRODUCT_EXT_IO_BATCH,
+                                 **PRODUCT_EXT_STEP_BATCH}.items():
             if hasattr(self.lib, sym):  # not the oracle, nor an older library under GPQHE_LIB
                 f = getattr(self.lib, sym)
                 f.restype = res
@@ -351,6 +359,21 @@ class Engine:
         [count][2][nlimbs][n] -> y_ptr [count][2][nlimbs-1][n] (include/gpqhe_ext_batch.h)."""
         M = _cplx(M)
         self._ext("he_gemv_bsgs_batch")(y_ptr, M.ctypes.data, x_ptr, count, nlimbs, rk, g)
+
+    def gemv2_bsgs_batch(self, y_ptr, Ma, xa_ptr, Mb, xb_ptr, count, nlimbs, rk, g=0):
+        """y = Ma xa + Mb xb by one BSGS over both operands, `count` ciphertexts
+        in device memory: xa_ptr, xb_ptr [count][2][nlimbs][n] -> y_ptr
+        [count][2][nlimbs-1][n] (include/gpqhe_ext_step_batch.h)."""
+        Ma, Mb = _cplx(Ma), _cplx(Mb)
+        self._ext("he_gemv2_bsgs_batch")(y_ptr, Ma.ctypes.data, xa_ptr, Mb.ctypes.data, xb_ptr, count, nlimbs, rk, g)
+
+    def hempc_step_batch(self, up_ptr, Ma, Mb, xhat_ptr, xr_ptr, uhat_ptr, ur_ptr, count, nlimbs, rk, g=0):
+        """ctr_hempc over `count` loops: up = moddown(uhat) - (Ma (xhat - xr) +
+        Mb (uhat - ur)); four inputs [count][2][nlimbs][n] -> up_ptr
+        [count][2][nlimbs-1][n], device memory (include/gpqhe_ext_step_batch.h)."""
+        Ma, Mb = _cplx(Ma), _cplx(Mb)
+        self._ext("he_hempc_step_batch")(up_ptr, Ma.ctypes.data, Mb.ctypes.data, xhat_ptr, xr_ptr, uhat_ptr, ur_ptr,
+                                         count, nlimbs, rk, g)
 
     def enc_pk_batch(self, x_ptr, zs, pk, slots, scale, nlimbs):
         """he_ecd_ex + he_enc_pk of the rows of zs [count][slots] into device
