@@ -4,7 +4,7 @@
 // reference src/ctr.c:445-618 and src/hempc.c:216-274 (see gpqhe.h).
 #include "gpqhe_internal.h"
 #include "../../include/gpqhe_ext.h"
-#include "../../include/gpqhe_ext_batch.h"  // (and gpqhe_ext_io_batch.h, gpqhe_ext_step_batch.h)
+#include "../../include/gpqhe_ext_batch.h"  // (and gpqhe_ext_io_batch.h, gpqhe_ext_step_batch.h, gpqhe_ext_rows_batch.h)
 
 #include <math.h>
 #include <stdio.h>
@@ -39,6 +39,7 @@ static unsigned env_u(const char *name, unsigned dflt);
 void gemv_cache_clear();
 static void bsgs_cache_clear();
 static void bsgs2_cache_clear();
+static void rows_cache_clear();
 
 void *pool_alloc(size_t bytes)
 {
@@ -1130,6 +1131,7 @@ extern "C" void hectx_exit(void)
   gemv_cache_clear();
   bsgs_cache_clear();
   bsgs2_cache_clear();
+  rows_cache_clear();
   fold_cache_clear();
   g_key_gen++;
   tables_free();
@@ -3997,6 +3999,284 @@ extern "C" void he_hempc_step_batch(uint64_t *up, const gpqhe_complex_t Ma[], co
   const StepIn st{xhat, xr, uhat, ur};
   bsgs2_run("he_hempc_step_batch", up, (const double *)Ma, (const double *)Mb, nullptr, nullptr, &st, count, nlimbs, rk,
             g);
+}
+
+// ---------------------------------------------------------------------------
+// he_gemv2_rows_batch / he_hempc_step_rows_batch / he_genrk_rows
+// (include/gpqhe_ext_rows_batch.h): the leading `rows` rows of Ma xa + Mb xb
+// by row folding.  With m' = 2^ceil(log2 rows), each matrix has at most m'
+// extended diagonals E_i (row k mod m' of the matrix at column k + i, zero
+// where k mod m' >= rows); their products with rot(x, i) are summed, rescaled,
+// and log2(s / m') rotate-and-add steps at level lvl - 1 gather the partial
+// sums: 2 (m' - 1) + log2(s / m') key switches per ciphertext.  The baby
+// rotations, the inner sums and the rescale are he_gemv2_bsgs_batch's stages
+// with one "giant step" (no giant rotation); the fold's additions are
+// rows_batch.hip's, the last one of a step fused with the step's tail.
+//
+// The row plan: one cache entry per (the leading rows s entries of Ma, of Mb,
+// level, rows), in a list of its own with bsgs2_plan_get's rules -- one lookup
+// per call before the first launch, every eviction there, the entry owns its
+// blocks, bounded by diag_cache_cap(), a larger plan lives in the call's
+// holder, hectx_exit empties it.
+// ---------------------------------------------------------------------------
+struct RowsPlan {
+  std::vector<double> Ma, Mb;  // the leading rows of the matrices it was made from
+  unsigned s = 0, lvl = 0, rows = 0;
+  BsgsPlan a, b;               // .baby: the i of each operand's non-zero E_i, ascending (host lists only)
+  uint64_t *pts = nullptr;     // [a.baby.size() + b.baby.size()][lvl][n]: a's extended diagonals, then b's
+  int *tab_dev = nullptr;      // [1][baby slots of a | of b] -> index into pts (the identity)
+  size_t bytes = 0;
+};
+static std::list<RowsPlan> g_rows;
+static size_t g_rows_bytes = 0;
+
+static void rows_cache_clear()
+{
+  for (RowsPlan &p : g_rows) {
+    pool_free(p.pts);
+    pool_free(p.tab_dev);
+  }
+  g_rows.clear();
+  g_rows_bytes = 0;
+}
+
+struct RowsPlanHold {
+  RowsPlan tmp;
+  std::unique_ptr<Ws> pts, tab;
+};
+
+static unsigned rows_pow2(unsigned rows)
+{
+  unsigned mp = 1;
+  while (mp < rows)
+    mp <<= 1;
+  return mp;
+}
+
+// E_i of M: v [s] complex; false when it is all zero.
+static bool rows_diag(std::vector<double> &v, const double *Md, unsigned i, unsigned rows, unsigned mp)
+{
+  const unsigned s = G.slots;
+  bool nz = false;
+  for (unsigned k = 0; k < s; k++) {
+    const unsigned row = k % mp;
+    const size_t src = (size_t)row * s + (k + i) % s;
+    v[2 * k] = row < rows ? Md[2 * src] : 0.0;
+    v[2 * k + 1] = row < rows ? Md[2 * src + 1] : 0.0;
+    nz |= v[2 * k] != 0.0 || v[2 * k + 1] != 0.0;
+  }
+  return nz;
+}
+
+static const RowsPlan *rows_plan_get(RowsPlanHold &h, const double *Ma, const double *Mb, unsigned lvl, unsigned rows)
+{
+  const unsigned s = G.slots, mp = rows_pow2(rows);
+  const size_t pw = (size_t)lvl * G.n, mwords = 2 * (size_t)rows * s;
+  for (auto it = g_rows.begin(); it != g_rows.end(); ++it)
+    if (it->s == s && it->lvl == lvl && it->rows == rows && !memcmp(it->Ma.data(), Ma, mwords * 8) &&
+        !memcmp(it->Mb.data(), Mb, mwords * 8)) {
+      g_rows.splice(g_rows.begin(), g_rows, it);
+      return &g_rows.front();
+    }
+  RowsPlan &tmp = h.tmp;
+  std::vector<double> v(2 * (size_t)s);
+  for (unsigned i = 0; i < mp; i++) {
+    if (rows_diag(v, Ma, i, rows, mp))
+      tmp.a.baby.push_back(i);
+    if (rows_diag(v, Mb, i, rows, mp))
+      tmp.b.baby.push_back(i);
+  }
+  const size_t na = tmp.a.baby.size(), ndiag = na + tmp.b.baby.size();
+  if (!ndiag)
+    return &tmp;  // both matrices zero in their leading rows: no blocks
+  std::vector<int> tab(ndiag);
+  for (size_t e = 0; e < ndiag; e++)
+    tab[e] = (int)e;
+  const size_t tabw = (ndiag * sizeof(int) + 7) / 8;
+  tmp.bytes = ndiag * pw * 8;
+  if (tmp.bytes > diag_cache_cap()) {
+    h.pts.reset(new Ws(ndiag * pw));
+    h.tab.reset(new Ws(tabw));
+    tmp.pts = h.pts->p;
+    tmp.tab_dev = (int *)h.tab->p;
+  } else {
+    while (!g_rows.empty() && g_rows_bytes + tmp.bytes > diag_cache_cap()) {
+      pool_free(g_rows.back().pts);
+      pool_free(g_rows.back().tab_dev);
+      g_rows_bytes -= g_rows.back().bytes;
+      g_rows.pop_back();
+    }
+    tmp.pts = (uint64_t *)pool_alloc(tmp.bytes);
+    tmp.tab_dev = (int *)pool_alloc(tabw * 8);
+  }
+  unsigned mods[GPQHE_MAXMOD];
+  for (unsigned l = 0; l < lvl; l++)
+    mods[l] = l;
+  for (size_t e = 0; e < ndiag; e++) {
+    rows_diag(v, e < na ? Ma : Mb, e < na ? tmp.a.baby[e] : tmp.b.baby[e - na], rows, mp);
+    encode_limbs(tmp.pts + e * pw, v.data(), s, (double)G.q[lvl - 1], mods, lvl);
+  }
+  upload(tmp.tab_dev, tab.data(), ndiag * sizeof(int));
+  if (h.pts)
+    return &tmp;
+  tmp.Ma.assign(Ma, Ma + mwords);  // the owned copies: made on a miss only
+  tmp.Mb.assign(Mb, Mb + mwords);
+  tmp.s = s;
+  tmp.lvl = lvl;
+  tmp.rows = rows;
+  g_rows_bytes += tmp.bytes;
+  g_rows.push_front(std::move(tmp));
+  return &g_rows.front();
+}
+
+extern "C" void he_genrk_rows(he_evk_t rk[], const poly_mpi_t *sk, unsigned int rows)
+{
+  check_ctx();
+  const unsigned s = G.slots;
+  if (!rows || rows > s)
+    gpqhe_die("he_genrk_rows: rows = %u, slots = %u", rows, s);
+  const unsigned mp = rows_pow2(rows);
+  if (rk[0].data)
+    obj_free(&rk[0]);
+  rk[0].galois = 1;
+  for (unsigned r = 1; r < s; r++) {
+    const bool fold = r % mp == 0 && !(r / mp & (r / mp - 1));  // m' 2^t
+    if (r < mp || fold)
+      gen_rot_key(&rk[r], galois_of_rot(r), sk);
+    else if (rk[r].data)
+      he_free_evk(&rk[r]);
+  }
+}
+
+// One chunk of cnt ciphertexts: ka / kb the baby rotations of each operand,
+// fold the rotations m', 2 m', .. < s.  st as in bsgs2_chunk; its tail is the
+// last fold step's kernel, or k_step_tail_batch where there is no fold.
+static void rows_chunk(uint64_t *y, const uint64_t *xa, const uint64_t *xb, const StepIn *st, unsigned cnt,
+                       unsigned lvl, const RowsPlan &plan, const BsgsKeys &ka, const BsgsKeys &kb,
+                       const std::vector<unsigned> &fold, const he_evk_t rk[], size_t budget)
+{
+  const size_t n = G.n, pw = (size_t)lvl * n, cw = 2 * pw, sw = (size_t)cnt * cw;  // words: ciphertext, slot
+  const size_t ow = 2 * (size_t)(lvl - 1) * n;                                     // ... of y
+  const unsigned nbs = ka.nbs + kb.nbs;
+  Ws B((size_t)nbs * sw), U(sw);
+  uint64_t *Ba = B.p, *Bb = B.p + (size_t)ka.nbs * sw;
+
+  Ws Xd(st && !ka.has0 ? sw : 0), Ud(st && !kb.has0 ? sw : 0);
+  if (st) {
+    uint64_t *xd = ka.has0 ? Ba : Xd.p, *ud = kb.has0 ? Bb : Ud.p;
+    k_step_diff_batch(xd, ud, st->xhat, st->xr, st->uhat, st->ur, lvl, cnt);
+    xa = xd;
+    xb = ud;
+  }
+
+  // baby rotations of both operands, the sum over all of their extended
+  // diagonals (one "giant step"), the rescale by q_top into y
+  const bool win = gemv_win_on(lvl);
+  bsgs2_baby(Ba, xa, cnt, lvl, ka, rk, budget, win);
+  bsgs2_baby(Bb, xb, cnt, lvl, kb, rk, budget, win);
+  k_bsgs_inner_batch(U.p, B.p, plan.pts, plan.tab_dev, 1, nbs, nbs, lvl, cnt);
+  k_moddown(y, (size_t)(lvl - 1) * n, U.p, pw, 2 * cnt, lvl, 2);
+
+  // the fold at level lvl - 1: the whole chunk rotated into R (the baby slots'
+  // buffer: the inner sums were the last to read it), then accumulated
+  uint64_t *R = B.p;
+  const bool winf = gemv_win_on(lvl - 1);
+  for (size_t t = 0; t < fold.size(); t++) {
+    if (winf) {
+      const RotFold &f = bsgs_rot_fold(fold[t], lvl - 1, rk);
+      RotFoldUse use(f);
+      k_gemv_batch(R, y, cnt, lvl - 1, f.K, &f.rot, 1, 0);
+    } else {
+      for (unsigned c = 0; c < cnt; c++) {
+        he_ct_t cx = ct_view(y + c * ow, lvl - 1), co = ct_view(R + c * ow, lvl - 1);
+        he_rot(&co, &cx, fold[t], rk);
+      }
+    }
+    if (st && t + 1 == fold.size())
+      k_rows_fold_tail_batch(y, R, st->uhat, lvl, cnt);
+    else
+      k_rows_fold_add_batch(y, R, lvl - 1, cnt);
+  }
+  if (st && fold.empty())
+    k_step_tail_batch(y, st->uhat, lvl, cnt);
+}
+
+static void rows_run(const char *who, uint64_t *y, const double *Ma, const double *Mb, const uint64_t *xa,
+                     const uint64_t *xb, const StepIn *st, size_t count, unsigned lvl, const he_evk_t rk[],
+                     unsigned rows)
+{
+  check_ctx();
+  const unsigned s = G.slots;
+  if (lvl < 2 || lvl > G.L)
+    gpqhe_die("%s: bad level %u", who, lvl);
+  if (!rows || rows > s)
+    gpqhe_die("%s: rows = %u, slots = %u", who, rows, s);
+  const unsigned nm = lvl + G.K, ndig = (lvl + G.alpha - 1) / G.alpha;
+  const size_t n = G.n, pw = (size_t)lvl * n, in_words = 2 * pw, out_words = 2 * (size_t)(lvl - 1) * n;
+  if (!count)
+    return;
+  const uint64_t *ins[4] = {st ? st->xhat : xa, st ? st->xr : xb, st ? st->uhat : nullptr, st ? st->ur : nullptr};
+  for (const uint64_t *x : ins)
+    if (x && y < x + count * in_words && x < y + count * out_words)
+      gpqhe_die("%s: output overlaps an input", who);
+
+  RowsPlanHold hold;
+  const RowsPlan *plan = rows_plan_get(hold, Ma, Mb, lvl, rows);
+  if (plan->a.baby.empty() && plan->b.baby.empty()) {  // y = 0, up = the lower limbs of uhat
+    HIP_CHECK(hipMemsetAsync(y, 0, count * out_words * 8, G.stream));
+    for (size_t c0 = 0; st && c0 < count; c0 += 16384) {
+      const unsigned cnt = (unsigned)std::min<size_t>(16384, count - c0);
+      k_step_tail_batch(y + c0 * out_words, st->uhat + c0 * in_words, lvl, cnt);
+    }
+    return;
+  }
+  // every key is found before anything is launched
+  const BsgsKeys ka = bsgs_find_keys(plan->a, rk, 1), kb = bsgs_find_keys(plan->b, rk, 1);
+  std::vector<unsigned> fold;
+  for (unsigned r = rows_pow2(rows); r < s; r <<= 1) {
+    find_rot_key(rk, r, galois_of_rot(r));
+    fold.push_back(r);
+  }
+
+  // a ciphertext's share of a chunk, in words of one ciphertext (2 lvl n): the
+  // baby slots of both operands (later the rotated copy of the fold, which is
+  // smaller), the sum, and 1 per operand of a step whose difference has no
+  // slot 0 to live in; on the windowed path k_gemv_batch's workspace besides
+  const size_t budget = bsgs_budget();
+  const size_t slots_ct = ka.nbs + kb.nbs + 1 + (st ? !ka.has0 + !kb.has0 : 0);
+  const size_t per_ct =
+    slots_ct * 2 * pw + (gemv_win_on(lvl) ? ((size_t)lvl + (size_t)ndig * nm + 2 * (size_t)nm) * n : 0);
+  size_t chunk = std::min<size_t>(std::max<size_t>(1, budget / per_ct), 16384);
+  if (const char *e = getenv("GPQHE_BSGS_CHUNK"))  // test hook: several chunks on a small batch
+    chunk = std::max<size_t>(1, std::min<size_t>(chunk, strtoul(e, nullptr, 0)));
+  else  // equal chunks, as he_gemv_bsgs_batch
+    chunk = (count + (count + chunk - 1) / chunk - 1) / ((count + chunk - 1) / chunk);
+  for (size_t c0 = 0; c0 < count; c0 += chunk) {
+    const unsigned cnt = (unsigned)std::min(chunk, count - c0);
+    const size_t o = c0 * in_words;
+    const StepIn sc = st ? StepIn{st->xhat + o, st->xr + o, st->uhat + o, st->ur + o} : StepIn{};
+    rows_chunk(y + c0 * out_words, st ? nullptr : xa + o, st ? nullptr : xb + o, st ? &sc : nullptr, cnt, lvl, *plan,
+               ka, kb, fold, rk, budget);
+  }
+}
+
+extern "C" void he_gemv2_rows_batch(uint64_t *y, const gpqhe_complex_t Ma[], const uint64_t *xa,
+                                    const gpqhe_complex_t Mb[], const uint64_t *xb, size_t count, unsigned int nlimbs,
+                                    const he_evk_t rk[], unsigned int rows)
+{
+  HPROF("gemv2_rows_batch");
+  rows_run("he_gemv2_rows_batch", y, (const double *)Ma, (const double *)Mb, xa, xb, nullptr, count, nlimbs, rk, rows);
+}
+
+extern "C" void he_hempc_step_rows_batch(uint64_t *up, const gpqhe_complex_t Ma[], const gpqhe_complex_t Mb[],
+                                         const uint64_t *xhat, const uint64_t *xr, const uint64_t *uhat,
+                                         const uint64_t *ur, size_t count, unsigned int nlimbs, const he_evk_t rk[],
+                                         unsigned int rows)
+{
+  HPROF("hempc_step_rows_batch");
+  const StepIn st{xhat, xr, uhat, ur};
+  rows_run("he_hempc_step_rows_batch", up, (const double *)Ma, (const double *)Mb, nullptr, nullptr, &st, count, nlimbs,
+           rk, rows);
 }
 
 // ---------------------------------------------------------------------------

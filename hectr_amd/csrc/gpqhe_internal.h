@@ -477,7 +477,8 @@ enum KClass {
   KC_NTT2_COLS_INV, KC_KS_COLS4, KC_NTT_SMALL_FWD, KC_NTT_SMALL_INV, KC_GEMV_INNER, KC_KSQ_DROP, KC_KSQ_KEEP,
   KC_MODUP_SMALL, KC_DOWN_SMALL, KC_GEMV_WIN, KC_GEMV_FBC, KC_GEMV_FOLD, KC_GEMV_C0, KC_BSGS_KS, KC_BSGS_INNER,
   KC_BSGS_SUM, KC_BSGS_INNER_BATCH, KC_BSGS_SUM_BATCH, KC_FFT_ENC_BATCH, KC_ENC_SAMPLE_BATCH, KC_ENC_COMBINE_BATCH,
-  KC_DEC_FOLD, KC_FOLD_DCD, KC_DEC_BATCH, KC_STEP_DIFF_BATCH, KC_STEP_TAIL_BATCH, KC_COUNT
+  KC_DEC_FOLD, KC_FOLD_DCD, KC_DEC_BATCH, KC_STEP_DIFF_BATCH, KC_STEP_TAIL_BATCH,
+  KC_ROWS_FOLD_ADD_BATCH, KC_ROWS_FOLD_TAIL_BATCH, KC_COUNT
 };
 struct ProfScope {
   int cls;
@@ -575,6 +576,12 @@ void k_step_diff_batch(uint64_t *xd, uint64_t *ud, const uint64_t *xhat, const u
                        const uint64_t *ur, unsigned lvl, unsigned cnt);
 // up [cnt][2][lvl-1][n] <- the limbs below lvl - 1 of uhat [cnt][2][lvl][n] - up
 void k_step_tail_batch(uint64_t *up, const uint64_t *uhat, unsigned lvl, unsigned cnt);
+// he_gemv2_rows_batch / he_hempc_step_rows_batch (rows_batch.hip): a fold step
+// over a chunk of cnt ciphertexts, R the chunk rotated, same layout as y.
+// y [cnt][2][nl][n] += R
+void k_rows_fold_add_batch(uint64_t *y, const uint64_t *R, unsigned nl, unsigned cnt);
+// up [cnt][2][lvl-1][n] <- the limbs below lvl - 1 of uhat [cnt][2][lvl][n] - (up + R)
+void k_rows_fold_tail_batch(uint64_t *up, const uint64_t *R, const uint64_t *uhat, unsigned lvl, unsigned cnt);
 void tables_upload();
 void tables_prewarm();
 void tables_free();

@@ -51,7 +51,8 @@ static const char *kc_names[KC_COUNT] = {
   "gemv_win_kernel", "gemv_fbc_kernel", "gemv_fold_kernel", "gemv_c0_kernel", "bsgs_ks_kernel",
   "bsgs_inner_kernel", "bsgs_sum_kernel", "bsgs_inner_batch_kernel", "bsgs_sum_batch_kernel",
   "fft_enc_batch_kernel", "enc_sample_batch_kernel", "enc_combine_batch_kernel", "dec_fold_kernel",
-  "fold_dcd_kernel", "dec_batch_kernel", "step_diff_batch_kernel", "step_tail_batch_kernel"};
+  "fold_dcd_kernel", "dec_batch_kernel", "step_diff_batch_kernel", "step_tail_batch_kernel",
+  "rows_fold_add_batch_kernel", "rows_fold_tail_batch_kernel"};
 
 struct ProfEntry {
   int cls;

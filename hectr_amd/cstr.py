@@ -433,12 +433,15 @@ class BatchedEncryptedRegulator:
     calls: one he_enc_pk_batch of the 4 count vectors (into one device array
     sliced four ways), he_hempc_step_batch, he_dec_dcd_batch.  The loops share
     the problem's gain matrices, the key pair and the he_genrk_bsgs(g) rotation
-    keys.  Device memory comes from torch."""
+    keys.  With rows=k (k >= nu: only the first nu entries of the result are
+    used) the step is he_hempc_step_rows_batch, the row-folded product of the k
+    leading rows, on the he_genrk_rows(k) keys.  Device memory comes from torch."""
 
     def __init__(self, engine, problem: CstrProblem, count, g=0, seed=None, logn=12, logq=109, log_delta=50,
-                 init=True):
+                 init=True, rows=None):
         import torch
-        self.e, self.pb, self.count, self.g = engine, problem, count, g
+        self.e, self.pb, self.count, self.g, self.rows = engine, problem, count, g, rows
+        assert rows is None or problem.nu <= rows <= problem.slots
         if init:
             engine.init(logn, logq, problem.slots, log_delta)
         if seed is not None:
@@ -447,7 +450,10 @@ class BatchedEncryptedRegulator:
         self.pk, self.sk = engine.pk(), engine.sk()
         self.rk = engine.evks(s)
         engine.keypair(self.pk, self.sk)
-        engine.genrk_bsgs(self.rk, self.sk, g)
+        if rows is None:
+            engine.genrk_bsgs(self.rk, self.sk, g)
+        else:
+            engine.genrk_rows(self.rk, self.sk, rows)
         self.lvl, self.scale = engine.L, engine.info.delta
         self.cw = 2 * self.lvl * engine.n                  # words of one input ciphertext
         self.x = torch.zeros(4 * count * self.cw, dtype=torch.int64, device="cuda")
@@ -466,8 +472,12 @@ class BatchedEncryptedRegulator:
             zs[b, :, :v.shape[1]] = v
         e.enc_pk_batch(self.x.data_ptr(), zs.reshape(4 * cnt, s), self.pk, s, self.scale, self.lvl)
         part = [self.x.data_ptr() + 8 * b * cnt * self.cw for b in range(4)]
-        e.hempc_step_batch(self.up.data_ptr(), self.MAz, self.MBz, part[0], part[1], part[2], part[3], cnt, self.lvl,
-                           self.rk, self.g)
+        if self.rows is None:
+            e.hempc_step_batch(self.up.data_ptr(), self.MAz, self.MBz, part[0], part[1], part[2], part[3], cnt,
+                               self.lvl, self.rk, self.g)
+        else:
+            e.hempc_step_rows_batch(self.up.data_ptr(), self.MAz, self.MBz, part[0], part[1], part[2], part[3], cnt,
+                                    self.lvl, self.rk, self.rows)
         uz = e.dec_dcd_batch(self.up.data_ptr(), cnt, self.lvl - 1, self.scale, self.sk, s)
         assert np.all(uz.imag < HECTR_SMALL), "imaginary part too large (src/ctr.c:493-494)"
         self.timings.append(time.perf_counter() - t0)

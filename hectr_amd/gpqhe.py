@@ -178,6 +178,14 @@ PRODUCT_EXT_STEP_BATCH = {
     "he_hempc_step_batch": (None, [VP, VP, VP, VP, VP, VP, VP, C.c_size_t, C.c_uint, OBJ, C.c_uint]),
 }
 
+#: include/gpqhe_ext_rows_batch.h (part of gpqhe_ext_batch.h): the leading rows
+#: of the step by row folding, product only, bound like PRODUCT_EXT
+PRODUCT_EXT_ROWS_BATCH = {
+    "he_genrk_rows": (None, [OBJ, OBJ, C.c_uint]),
+    "he_gemv2_rows_batch": (None, [VP, VP, VP, VP, VP, C.c_size_t, C.c_uint, OBJ, C.c_uint]),
+    "he_hempc_step_rows_batch": (None, [VP, VP, VP, VP, VP, VP, VP, C.c_size_t, C.c_uint, OBJ, C.c_uint]),
+}
+
 
 def _cplx(z) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(z, dtype=np.complex128))
@@ -200,7 +208,7 @@ class Engine:
             f.restype = res
             f.argtypes = args
         for sym, (res, args) in {**PRODUCT_EXT, **PRODUCT_EXT_BATCH, **PRODUCT_EXT_IO_BATCH,
-                                 **PRODUCT_EXT_STEP_BATCH}.items():
+                                 **PRODUCT_EXT_STEP_BATCH, **PRODUCT_EXT_ROWS_BATCH}.items():
             if hasattr(self.lib, sym):  # not the oracle, nor an older library under GPQHE_LIB
                 f = getattr(self.lib, sym)
                 f.restype = res
@@ -374,6 +382,27 @@ class Engine:
         Ma, Mb = _cplx(Ma), _cplx(Mb)
         self._ext("he_hempc_step_batch")(up_ptr, Ma.ctypes.data, Mb.ctypes.data, xhat_ptr, xr_ptr, uhat_ptr, ur_ptr,
                                          count, nlimbs, rk, g)
+
+    def genrk_rows(self, rk, sk, rows):
+        """The rotation keys the row-folded product of `rows` leading rows can
+        need, into rk[slots] (include/gpqhe_ext_rows_batch.h)."""
+        self._ext("he_genrk_rows")(rk, C.byref(sk), rows)
+
+    def gemv2_rows_batch(self, y_ptr, Ma, xa_ptr, Mb, xb_ptr, count, nlimbs, rk, rows):
+        """The leading `rows` rows of Ma xa + Mb xb by row folding, `count`
+        ciphertexts in device memory: xa_ptr, xb_ptr [count][2][nlimbs][n] ->
+        y_ptr [count][2][nlimbs-1][n] (include/gpqhe_ext_rows_batch.h)."""
+        Ma, Mb = _cplx(Ma), _cplx(Mb)
+        self._ext("he_gemv2_rows_batch")(y_ptr, Ma.ctypes.data, xa_ptr, Mb.ctypes.data, xb_ptr, count, nlimbs, rk, rows)
+
+    def hempc_step_rows_batch(self, up_ptr, Ma, Mb, xhat_ptr, xr_ptr, uhat_ptr, ur_ptr, count, nlimbs, rk, rows):
+        """ctr_hempc over `count` loops with its product by row folding: the
+        first `rows` slots of up = moddown(uhat) - (Ma (xhat - xr) + Mb (uhat -
+        ur)); four inputs [count][2][nlimbs][n] -> up_ptr [count][2][nlimbs-1][n],
+        device memory (include/gpqhe_ext_rows_batch.h)."""
+        Ma, Mb = _cplx(Ma), _cplx(Mb)
+        self._ext("he_hempc_step_rows_batch")(up_ptr, Ma.ctypes.data, Mb.ctypes.data, xhat_ptr, xr_ptr, uhat_ptr,
+                                              ur_ptr, count, nlimbs, rk, rows)
 
     def enc_pk_batch(self, x_ptr, zs, pk, slots, scale, nlimbs):
         """he_ecd_ex + he_enc_pk of the rows of zs [count][slots] into device

@@ -34,5 +34,6 @@ void he_gemv_bsgs_batch(uint64_t *y, const gpqhe_complex_t M[], const uint64_t *
 /* the two ends of the batch entry points: he_enc_pk_batch, he_dec_dcd_batch */
 #include "gpqhe_ext_io_batch.h"
 #include "gpqhe_ext_step_batch.h"
+#include "gpqhe_ext_rows_batch.h"
 
 #endif /* GPQHE_EXT_BATCH_H */
