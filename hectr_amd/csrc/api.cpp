@@ -4,7 +4,7 @@
 // reference src/ctr.c:445-618 and src/hempc.c:216-274 (see gpqhe.h).
 #include "gpqhe_internal.h"
 #include "../../include/gpqhe_ext.h"
-#include "../../include/gpqhe_ext_batch.h"  // (and gpqhe_ext_io_batch.h, gpqhe_ext_step_batch.h, gpqhe_ext_rows_batch.h)
+#include "../../include/gpqhe_ext_batch.h"  // (and gpqhe_ext_io_batch.h, gpqhe_ext_step_batch.h, gpqhe_ext_rows_batch.h, gpqhe_ext_packed_batch.h)
 
 #include <math.h>
 #include <stdio.h>
@@ -4018,11 +4018,19 @@ extern "C" void he_hempc_step_batch(uint64_t *up, const gpqhe_complex_t Ma[], co
 // per call before the first launch, every eviction there, the entry owns its
 // blocks, bounded by diag_cache_cap(), a larger plan lives in the call's
 // holder, hectx_exit empties it.
+//
+// The packed forms (include/gpqhe_ext_packed_batch.h: he_gemv2_packed_batch,
+// he_hempc_step_packed_batch, he_genrk_packed) are the same code at a stride:
+// the context's S slots hold P = S / sl loops of sl slots, entry k of loop p
+// at slot k P + p, so E_i is filled over S slots from loop p's own matrix
+// (nmat = P) or the shared one (nmat = 1), baby rotation i is rotation i P and
+// fold step r is r P.  The entry points above are sl = S, nmat = 1 (P = 1);
+// the plan's key holds sl and nmat besides.
 // ---------------------------------------------------------------------------
 struct RowsPlan {
-  std::vector<double> Ma, Mb;  // the leading rows of the matrices it was made from
-  unsigned s = 0, lvl = 0, rows = 0;
-  BsgsPlan a, b;               // .baby: the i of each operand's non-zero E_i, ascending (host lists only)
+  std::vector<double> Ma, Mb;  // the leading rows of the matrices it was made from ([nmat][rows][sl])
+  unsigned s = 0, lvl = 0, rows = 0, sl = 0, nmat = 0;
+  BsgsPlan a, b;               // .baby: the rotation i P of each operand's non-zero E_i, ascending (host lists only)
   uint64_t *pts = nullptr;     // [a.baby.size() + b.baby.size()][lvl][n]: a's extended diagonals, then b's
   int *tab_dev = nullptr;      // [1][baby slots of a | of b] -> index into pts (the identity)
   size_t bytes = 0;
@@ -4053,38 +4061,42 @@ static unsigned rows_pow2(unsigned rows)
   return mp;
 }
 
-// E_i of M: v [s] complex; false when it is all zero.
-static bool rows_diag(std::vector<double> &v, const double *Md, unsigned i, unsigned rows, unsigned mp)
+// E_i of M ([nmat][rows][sl], loop p's matrix p mod nmat) over the context's
+// slots: v [S] complex, slot k P + p from row k mod m' of loop p's matrix at
+// column (k + i) mod sl; false when it is all zero.
+static bool rows_diag(std::vector<double> &v, const double *Md, unsigned i, unsigned rows, unsigned mp, unsigned sl,
+                      unsigned nmat)
 {
-  const unsigned s = G.slots;
+  const unsigned S = G.slots, P = S / sl;
   bool nz = false;
-  for (unsigned k = 0; k < s; k++) {
-    const unsigned row = k % mp;
-    const size_t src = (size_t)row * s + (k + i) % s;
-    v[2 * k] = row < rows ? Md[2 * src] : 0.0;
-    v[2 * k + 1] = row < rows ? Md[2 * src + 1] : 0.0;
-    nz |= v[2 * k] != 0.0 || v[2 * k + 1] != 0.0;
+  for (unsigned j = 0; j < S; j++) {
+    const unsigned k = j / P, p = j % P, row = k % mp;
+    const size_t src = ((size_t)(nmat > 1 ? p : 0) * rows + row) * sl + (k + i) % sl;
+    v[2 * j] = row < rows ? Md[2 * src] : 0.0;
+    v[2 * j + 1] = row < rows ? Md[2 * src + 1] : 0.0;
+    nz |= v[2 * j] != 0.0 || v[2 * j + 1] != 0.0;
   }
   return nz;
 }
 
-static const RowsPlan *rows_plan_get(RowsPlanHold &h, const double *Ma, const double *Mb, unsigned lvl, unsigned rows)
+static const RowsPlan *rows_plan_get(RowsPlanHold &h, const double *Ma, const double *Mb, unsigned lvl, unsigned rows,
+                                     unsigned sl, unsigned nmat)
 {
-  const unsigned s = G.slots, mp = rows_pow2(rows);
-  const size_t pw = (size_t)lvl * G.n, mwords = 2 * (size_t)rows * s;
+  const unsigned s = G.slots, P = s / sl, mp = rows_pow2(rows);
+  const size_t pw = (size_t)lvl * G.n, mwords = 2 * (size_t)nmat * rows * sl;
   for (auto it = g_rows.begin(); it != g_rows.end(); ++it)
-    if (it->s == s && it->lvl == lvl && it->rows == rows && !memcmp(it->Ma.data(), Ma, mwords * 8) &&
-        !memcmp(it->Mb.data(), Mb, mwords * 8)) {
+    if (it->s == s && it->lvl == lvl && it->rows == rows && it->sl == sl && it->nmat == nmat &&
+        !memcmp(it->Ma.data(), Ma, mwords * 8) && !memcmp(it->Mb.data(), Mb, mwords * 8)) {
       g_rows.splice(g_rows.begin(), g_rows, it);
       return &g_rows.front();
     }
   RowsPlan &tmp = h.tmp;
   std::vector<double> v(2 * (size_t)s);
   for (unsigned i = 0; i < mp; i++) {
-    if (rows_diag(v, Ma, i, rows, mp))
-      tmp.a.baby.push_back(i);
-    if (rows_diag(v, Mb, i, rows, mp))
-      tmp.b.baby.push_back(i);
+    if (rows_diag(v, Ma, i, rows, mp, sl, nmat))
+      tmp.a.baby.push_back(i * P);
+    if (rows_diag(v, Mb, i, rows, mp, sl, nmat))
+      tmp.b.baby.push_back(i * P);
   }
   const size_t na = tmp.a.baby.size(), ndiag = na + tmp.b.baby.size();
   if (!ndiag)
@@ -4113,7 +4125,7 @@ static const RowsPlan *rows_plan_get(RowsPlanHold &h, const double *Ma, const do
   for (unsigned l = 0; l < lvl; l++)
     mods[l] = l;
   for (size_t e = 0; e < ndiag; e++) {
-    rows_diag(v, e < na ? Ma : Mb, e < na ? tmp.a.baby[e] : tmp.b.baby[e - na], rows, mp);
+    rows_diag(v, e < na ? Ma : Mb, (e < na ? tmp.a.baby[e] : tmp.b.baby[e - na]) / P, rows, mp, sl, nmat);
     encode_limbs(tmp.pts + e * pw, v.data(), s, (double)G.q[lvl - 1], mods, lvl);
   }
   upload(tmp.tab_dev, tab.data(), ndiag * sizeof(int));
@@ -4124,28 +4136,51 @@ static const RowsPlan *rows_plan_get(RowsPlanHold &h, const double *Ma, const do
   tmp.s = s;
   tmp.lvl = lvl;
   tmp.rows = rows;
+  tmp.sl = sl;
+  tmp.nmat = nmat;
   g_rows_bytes += tmp.bytes;
   g_rows.push_front(std::move(tmp));
   return &g_rows.front();
 }
 
-extern "C" void he_genrk_rows(he_evk_t rk[], const poly_mpi_t *sk, unsigned int rows)
+// sl: the slots of one loop; it divides the context's (a power of two)
+static void rows_check_loops(const char *who, unsigned sl)
+{
+  if (!sl || (sl & (sl - 1)) || sl > G.slots)
+    gpqhe_die("%s: s = %u, slots = %u", who, sl, G.slots);
+}
+
+static void rows_genrk(const char *who, he_evk_t rk[], const poly_mpi_t *sk, unsigned sl, unsigned rows)
 {
   check_ctx();
   const unsigned s = G.slots;
-  if (!rows || rows > s)
-    gpqhe_die("he_genrk_rows: rows = %u, slots = %u", rows, s);
-  const unsigned mp = rows_pow2(rows);
+  rows_check_loops(who, sl);
+  if (!rows || rows > sl)
+    gpqhe_die("%s: rows = %u, slots = %u", who, rows, sl);
+  const unsigned mp = rows_pow2(rows), P = s / sl;
   if (rk[0].data)
     obj_free(&rk[0]);
   rk[0].galois = 1;
   for (unsigned r = 1; r < s; r++) {
-    const bool fold = r % mp == 0 && !(r / mp & (r / mp - 1));  // m' 2^t
-    if (r < mp || fold)
+    const unsigned i = r / P;                                   // the loops' own rotation (r = i P)
+    const bool fold = i % mp == 0 && !(i / mp & (i / mp - 1));  // m' 2^t
+    if (r % P == 0 && (i < mp || fold))
       gen_rot_key(&rk[r], galois_of_rot(r), sk);
     else if (rk[r].data)
       he_free_evk(&rk[r]);
   }
+}
+
+extern "C" void he_genrk_rows(he_evk_t rk[], const poly_mpi_t *sk, unsigned int rows)
+{
+  check_ctx();
+  rows_genrk("he_genrk_rows", rk, sk, G.slots, rows);
+}
+
+extern "C" void he_genrk_packed(he_evk_t rk[], const poly_mpi_t *sk, unsigned int s, unsigned int rows)
+{
+  check_ctx();
+  rows_genrk("he_genrk_packed", rk, sk, s, rows);
 }
 
 // One chunk of cnt ciphertexts: ka / kb the baby rotations of each operand,
@@ -4203,14 +4238,17 @@ static void rows_chunk(uint64_t *y, const uint64_t *xa, const uint64_t *xb, cons
 
 static void rows_run(const char *who, uint64_t *y, const double *Ma, const double *Mb, const uint64_t *xa,
                      const uint64_t *xb, const StepIn *st, size_t count, unsigned lvl, const he_evk_t rk[],
-                     unsigned rows)
+                     unsigned rows, unsigned sl, unsigned nmat)
 {
   check_ctx();
-  const unsigned s = G.slots;
   if (lvl < 2 || lvl > G.L)
     gpqhe_die("%s: bad level %u", who, lvl);
+  rows_check_loops(who, sl);
+  const unsigned s = sl, P = G.slots / sl;  // s: the slots of one loop
   if (!rows || rows > s)
     gpqhe_die("%s: rows = %u, slots = %u", who, rows, s);
+  if (nmat != 1 && nmat != P)
+    gpqhe_die("%s: %u matrices for %u loops", who, nmat, P);
   const unsigned nm = lvl + G.K, ndig = (lvl + G.alpha - 1) / G.alpha;
   const size_t n = G.n, pw = (size_t)lvl * n, in_words = 2 * pw, out_words = 2 * (size_t)(lvl - 1) * n;
   if (!count)
@@ -4221,7 +4259,7 @@ static void rows_run(const char *who, uint64_t *y, const double *Ma, const doubl
       gpqhe_die("%s: output overlaps an input", who);
 
   RowsPlanHold hold;
-  const RowsPlan *plan = rows_plan_get(hold, Ma, Mb, lvl, rows);
+  const RowsPlan *plan = rows_plan_get(hold, Ma, Mb, lvl, rows, sl, nmat);
   if (plan->a.baby.empty() && plan->b.baby.empty()) {  // y = 0, up = the lower limbs of uhat
     HIP_CHECK(hipMemsetAsync(y, 0, count * out_words * 8, G.stream));
     for (size_t c0 = 0; st && c0 < count; c0 += 16384) {
@@ -4234,8 +4272,8 @@ static void rows_run(const char *who, uint64_t *y, const double *Ma, const doubl
   const BsgsKeys ka = bsgs_find_keys(plan->a, rk, 1), kb = bsgs_find_keys(plan->b, rk, 1);
   std::vector<unsigned> fold;
   for (unsigned r = rows_pow2(rows); r < s; r <<= 1) {
-    find_rot_key(rk, r, galois_of_rot(r));
-    fold.push_back(r);
+    find_rot_key(rk, r * P, galois_of_rot(r * P));
+    fold.push_back(r * P);
   }
 
   // a ciphertext's share of a chunk, in words of one ciphertext (2 lvl n): the
@@ -4265,7 +4303,9 @@ extern "C" void he_gemv2_rows_batch(uint64_t *y, const gpqhe_complex_t Ma[], con
                                     const he_evk_t rk[], unsigned int rows)
 {
   HPROF("gemv2_rows_batch");
-  rows_run("he_gemv2_rows_batch", y, (const double *)Ma, (const double *)Mb, xa, xb, nullptr, count, nlimbs, rk, rows);
+  check_ctx();
+  rows_run("he_gemv2_rows_batch", y, (const double *)Ma, (const double *)Mb, xa, xb, nullptr, count, nlimbs, rk, rows,
+           G.slots, 1);
 }
 
 extern "C" void he_hempc_step_rows_batch(uint64_t *up, const gpqhe_complex_t Ma[], const gpqhe_complex_t Mb[],
@@ -4275,8 +4315,30 @@ extern "C" void he_hempc_step_rows_batch(uint64_t *up, const gpqhe_complex_t Ma[
 {
   HPROF("hempc_step_rows_batch");
   const StepIn st{xhat, xr, uhat, ur};
+  check_ctx();
   rows_run("he_hempc_step_rows_batch", up, (const double *)Ma, (const double *)Mb, nullptr, nullptr, &st, count, nlimbs,
-           rk, rows);
+           rk, rows, G.slots, 1);
+}
+
+extern "C" void he_gemv2_packed_batch(uint64_t *y, const gpqhe_complex_t Ma[], const uint64_t *xa,
+                                      const gpqhe_complex_t Mb[], const uint64_t *xb, size_t count,
+                                      unsigned int nlimbs, const he_evk_t rk[], unsigned int s, unsigned int rows,
+                                      unsigned int nmat)
+{
+  HPROF("gemv2_packed_batch");
+  rows_run("he_gemv2_packed_batch", y, (const double *)Ma, (const double *)Mb, xa, xb, nullptr, count, nlimbs, rk, rows,
+           s, nmat);
+}
+
+extern "C" void he_hempc_step_packed_batch(uint64_t *up, const gpqhe_complex_t Ma[], const gpqhe_complex_t Mb[],
+                                           const uint64_t *xhat, const uint64_t *xr, const uint64_t *uhat,
+                                           const uint64_t *ur, size_t count, unsigned int nlimbs, const he_evk_t rk[],
+                                           unsigned int s, unsigned int rows, unsigned int nmat)
+{
+  HPROF("hempc_step_packed_batch");
+  const StepIn st{xhat, xr, uhat, ur};
+  rows_run("he_hempc_step_packed_batch", up, (const double *)Ma, (const double *)Mb, nullptr, nullptr, &st, count,
+           nlimbs, rk, rows, s, nmat);
 }
 
 // ---------------------------------------------------------------------------
@@ -4311,20 +4373,20 @@ static void io_check(const char *who, unsigned nlimbs, unsigned slots)
     gpqhe_die("%s: bad slot count %u", who, slots);
 }
 
-extern "C" void he_enc_pk_batch(uint64_t *x, const gpqhe_complex_t z[], size_t count, unsigned int slots,
-                                double scale, unsigned int nlimbs, const he_pk_t *pk)
+// P = 0: z [count][s], the vectors as they are encoded.  P > 0 (the packed
+// form, s = P loops' slots): z [count][P][width] loop-major, slot k P + p of
+// ciphertext c from z[c][p][k], 0 for k >= width.
+static void enc_pk_run(const char *who, uint64_t *x, const gpqhe_complex_t z[], size_t count, unsigned s, double scale,
+                       unsigned lvl, const he_pk_t *pk, unsigned P, unsigned width)
 {
-  HPROF("enc_pk_batch");
-  check_ctx();
-  const unsigned lvl = nlimbs, s = slots;
-  io_check("he_enc_pk_batch", lvl, s);
+  io_check(who, lvl, s);
   if (!pk || !pk->data || pk->nlimbs < lvl)
-    gpqhe_die("he_enc_pk_batch: no public key at level %u", lvl);
+    gpqhe_die("%s: no public key at level %u", who, lvl);
   if (!count)
     return;
   if (!x || !z)
-    gpqhe_die("he_enc_pk_batch: null argument");
-  const size_t n = G.n, w = (size_t)lvl * n;
+    gpqhe_die("%s: null argument", who);
+  const size_t n = G.n, w = (size_t)lvl * n, zw = P ? (size_t)P * width : s;  // zw: a ciphertext's values of z
   // the streams of count he_enc_pk calls: base + 3 i + {0, 1, 2}
   const uint64_t base = G.counter;
   G.counter += 3 * (uint64_t)count;
@@ -4332,7 +4394,7 @@ extern "C" void he_enc_pk_batch(uint64_t *x, const gpqhe_complex_t z[], size_t c
   // the chunk's z, staged: at most 64 MiB of it), below it on the host (one
   // upload of the chunk's coefficients)
   const bool gpu = s >= gpu_ecd_min();
-  const size_t per_ct = 3 * w + 2 * (size_t)s * (gpu ? 2 : 1);
+  const size_t per_ct = 3 * w + 2 * (size_t)s * (gpu ? 2 : 1) + (gpu && P ? 2 * zw : 0);
   const size_t chunk = io_chunk(count, per_ct, gpu ? std::min<size_t>(16384, ((size_t)4 << 20) / s) : 16384);
   Ws ovf(gpu ? 1 : 0);
   if (gpu)
@@ -4341,15 +4403,29 @@ extern "C" void he_enc_pk_batch(uint64_t *x, const gpqhe_complex_t z[], size_t c
   for (size_t c0 = 0; c0 < count; c0 += chunk) {
     const unsigned cnt = (unsigned)std::min(chunk, count - c0);
     Ws vee(3 * cnt * w), coef(2 * (size_t)s * cnt);
-    const double *zc = (const double *)z + 2 * c0 * s;
+    const double *zc = (const double *)z + 2 * c0 * zw;
     if (gpu) {
       Ws work(2 * (size_t)s * cnt);
-      upload(work.p, zc, (size_t)cnt * s * 16);
+      if (P) {  // the chunk's z as given, interleaved on the device
+        Ws zin(2 * zw * cnt);
+        upload(zin.p, zc, (size_t)cnt * zw * 16);
+        k_pack_enc_gather((double *)work.p, (const double *)zin.p, s, P, width, cnt);
+      } else {
+        upload(work.p, zc, (size_t)cnt * s * 16);
+      }
       k_encode_slots_batch((int64_t *)coef.p, (double *)work.p, (int *)ovf.p, s, scale, cnt);
     } else {
       hv.resize(2 * (size_t)s * cnt);
-      for (unsigned i = 0; i < cnt; i++)
-        hm_encode_slots(hv.data() + 2 * (size_t)s * i, zc + 2 * (size_t)s * i, s, scale);
+      std::vector<double> il(P ? 2 * (size_t)s : 0);  // (zero for k >= width)
+      for (unsigned i = 0; i < cnt; i++) {
+        const double *zi = zc + 2 * zw * i;
+        for (unsigned p = 0; p < P; p++)
+          for (unsigned k = 0; k < width; k++) {
+            il[2 * ((size_t)k * P + p)] = zi[2 * ((size_t)p * width + k)];
+            il[2 * ((size_t)k * P + p) + 1] = zi[2 * ((size_t)p * width + k) + 1];
+          }
+        hm_encode_slots(hv.data() + 2 * (size_t)s * i, P ? il.data() : zi, s, scale);
+      }
       upload(coef.p, hv.data(), hv.size() * 8);
     }
     k_enc_sample_batch(vee.p, base + 3 * (uint64_t)c0, (const int64_t *)coef.p, s, lvl, cnt);
@@ -4366,47 +4442,91 @@ extern "C" void he_enc_pk_batch(uint64_t *x, const gpqhe_complex_t z[], size_t c
   }
 }
 
+extern "C" void he_enc_pk_batch(uint64_t *x, const gpqhe_complex_t z[], size_t count, unsigned int slots,
+                                double scale, unsigned int nlimbs, const he_pk_t *pk)
+{
+  HPROF("enc_pk_batch");
+  check_ctx();
+  enc_pk_run("he_enc_pk_batch", x, z, count, slots, scale, nlimbs, pk, 0, 0);
+}
+
+// The loops of a packed call: P = slots / s; dies unless s is a power of two
+// dividing the context's slots.
+static unsigned packed_loops(const char *who, unsigned s)
+{
+  if (!s || (s & (s - 1)) || s > G.slots)
+    gpqhe_die("%s: s = %u, slots = %u", who, s, G.slots);
+  return G.slots / s;
+}
+
+extern "C" void he_enc_pk_packed_batch(uint64_t *x, const gpqhe_complex_t z[], size_t count, unsigned int s,
+                                       unsigned int width, double scale, unsigned int nlimbs, const he_pk_t *pk)
+{
+  HPROF("enc_pk_packed_batch");
+  check_ctx();
+  const unsigned P = packed_loops("he_enc_pk_packed_batch", s);
+  if (!width || width > s)
+    gpqhe_die("he_enc_pk_packed_batch: width = %u, s = %u", width, s);
+  // (one loop of full width: z is the vector as it is encoded)
+  enc_pk_run("he_enc_pk_packed_batch", x, z, count, G.slots, scale, nlimbs, pk, P == 1 && width == s ? 0 : P, width);
+}
+
 // The folded path (k_dec_fold, k_fold_decode) reads each ciphertext once and
 // transforms 2 slots points per limb; it needs a gap n / 2 slots >= 2 and the
 // one-workgroup decoder.  Otherwise, and under GPQHE_DCD_FOLD=0: c0 + c1 s of
 // the chunk, its inverse transforms, and the single call's decoder per
 // ciphertext.  Same doubles either way.
-extern "C" void he_dec_dcd_batch(gpqhe_complex_t z[], const uint64_t *y, size_t count, unsigned int nlimbs,
-                                 double scale, unsigned int slots, const poly_mpi_t *sk)
+//
+// P = 0: z [count][s].  P > 0 (the packed form, s = P loops' slots): z
+// [count][P][rows], slot k P + p of ciphertext c into z[c][p][k], k < rows --
+// up to GPQHE_DCD_ONEPASS slots by the decoders' epilogue, so only those values
+// reach pinned memory; above it a gather of the chunk's decoded slots into a
+// compact device buffer, copied once.
+static void dec_dcd_run(const char *who, gpqhe_complex_t z[], const uint64_t *y, size_t count, unsigned nl,
+                        double scale, unsigned s, const poly_mpi_t *sk, unsigned P, unsigned rows)
 {
-  HPROF("dec_dcd_batch");
-  check_ctx();
-  const unsigned nl = nlimbs, s = slots;
-  io_check("he_dec_dcd_batch", nl, s);
+  io_check(who, nl, s);
   if (!sk || !sk->data || sk->nlimbs < nl)
-    gpqhe_die("he_dec_dcd_batch: no secret key at level %u", nl);
+    gpqhe_die("%s: no secret key at level %u", who, nl);
   if (!count)
     return;
   if (!y || !z)
-    gpqhe_die("he_dec_dcd_batch: null argument");
-  const size_t n = G.n, w = (size_t)nl * n, zb = (size_t)s * 16;
+    gpqhe_die("%s: null argument", who);
+  const size_t zw = P ? (size_t)P * rows : s;  // a ciphertext's values of z
+  const size_t n = G.n, w = (size_t)nl * n, zb = zw * 16;
   const bool fold = env_u("GPQHE_DCD_FOLD", 1) != 0 && s <= GPQHE_DCD_ONEPASS && 2 * (size_t)s < n;
   // up to GPQHE_DCD_ONEPASS slots the decoder writes each value once: straight
   // into pinned host memory (up to 64 MiB of it)
   const bool pinned = s <= GPQHE_DCD_ONEPASS && count * zb <= ((size_t)64 << 20);
-  Ws zdev(pinned ? 0 : 2 * (size_t)s * count);
+  const bool gather = P && s > GPQHE_DCD_ONEPASS;
+  Ws zdev(pinned ? 0 : 2 * zw * count);
   double *zd = pinned ? (double *)zpin(count * zb) : (double *)zdev.p;
-  const size_t chunk = io_chunk(count, fold ? 4 * (size_t)nl * s : w, 16384);
+  const size_t chunk = io_chunk(count, (fold ? 4 * (size_t)nl * s : w) + (gather ? 2 * (size_t)s : 0), 16384);
   for (size_t c0 = 0; c0 < count; c0 += chunk) {
     const unsigned cnt = (unsigned)std::min(chunk, count - c0);
     const uint64_t *yc = y + c0 * 2 * w;
-    double *zc = zd + 2 * c0 * s;
+    double *zc = zd + 2 * c0 * zw;
     if (fold) {
       const size_t fw = 2 * (size_t)s * nl * cnt;
       Ws F(fw), D(fw);
       k_dec_fold(F.p, yc, sk->data, s, nl, cnt);
-      k_fold_decode(zc, D.p, F.p, nl, s, scale, cnt);
+      if (P)
+        k_fold_decode_packed(zc, D.p, F.p, nl, s, scale, cnt, P, rows);
+      else
+        k_fold_decode(zc, D.p, F.p, nl, s, scale, cnt);
     } else {
-      Ws P(cnt * w);
-      k_dec_batch(P.p, yc, sk->data, nl, cnt);
-      ntt_polys(P.p, cnt, nl, true);
+      Ws pt(cnt * w), full(gather ? 2 * (size_t)s * cnt : 0);
+      k_dec_batch(pt.p, yc, sk->data, nl, cnt);
+      ntt_polys(pt.p, cnt, nl, true);
       for (unsigned i = 0; i < cnt; i++)
-        k_decode(zc + 2 * (size_t)s * i, P.p + i * w, nl, s, scale);
+        if (gather)
+          k_decode((double *)full.p + 2 * (size_t)s * i, pt.p + i * w, nl, s, scale);
+        else if (P)
+          k_decode_packed(zc + 2 * zw * i, pt.p + i * w, nl, s, scale, P, rows);
+        else
+          k_decode(zc + 2 * (size_t)s * i, pt.p + i * w, nl, s, scale);
+      if (gather)
+        k_pack_dcd_gather(zc, (const double *)full.p, s, P, rows, cnt);
     }
   }
   if (!pinned)
@@ -4414,6 +4534,26 @@ extern "C" void he_dec_dcd_batch(gpqhe_complex_t z[], const uint64_t *y, size_t 
   HIP_CHECK(hipStreamSynchronize(G.stream));
   if (pinned)
     memcpy(z, g_zpin, count * zb);
+}
+
+extern "C" void he_dec_dcd_batch(gpqhe_complex_t z[], const uint64_t *y, size_t count, unsigned int nlimbs,
+                                 double scale, unsigned int slots, const poly_mpi_t *sk)
+{
+  HPROF("dec_dcd_batch");
+  check_ctx();
+  dec_dcd_run("he_dec_dcd_batch", z, y, count, nlimbs, scale, slots, sk, 0, 0);
+}
+
+extern "C" void he_dec_dcd_packed_batch(gpqhe_complex_t z[], const uint64_t *y, size_t count, unsigned int nlimbs,
+                                        double scale, unsigned int s, unsigned int rows, const poly_mpi_t *sk)
+{
+  HPROF("dec_dcd_packed_batch");
+  check_ctx();
+  const unsigned P = packed_loops("he_dec_dcd_packed_batch", s);
+  if (!rows || rows > s)
+    gpqhe_die("he_dec_dcd_packed_batch: rows = %u, s = %u", rows, s);
+  // (one loop read whole: z is the decoded vector)
+  dec_dcd_run("he_dec_dcd_packed_batch", z, y, count, nlimbs, scale, G.slots, sk, P == 1 && rows == s ? 0 : P, rows);
 }
 
 // groups of ~224 MiB (ntt_batch), at most 65535 limbs a launch

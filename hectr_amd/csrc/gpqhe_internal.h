@@ -478,7 +478,8 @@ enum KClass {
   KC_MODUP_SMALL, KC_DOWN_SMALL, KC_GEMV_WIN, KC_GEMV_FBC, KC_GEMV_FOLD, KC_GEMV_C0, KC_BSGS_KS, KC_BSGS_INNER,
   KC_BSGS_SUM, KC_BSGS_INNER_BATCH, KC_BSGS_SUM_BATCH, KC_FFT_ENC_BATCH, KC_ENC_SAMPLE_BATCH, KC_ENC_COMBINE_BATCH,
   KC_DEC_FOLD, KC_FOLD_DCD, KC_DEC_BATCH, KC_STEP_DIFF_BATCH, KC_STEP_TAIL_BATCH,
-  KC_ROWS_FOLD_ADD_BATCH, KC_ROWS_FOLD_TAIL_BATCH, KC_COUNT
+  KC_ROWS_FOLD_ADD_BATCH, KC_ROWS_FOLD_TAIL_BATCH, KC_PACK_ENC_GATHER, KC_PACK_DCD_GATHER, KC_FOLD_DCD_PACKED,
+  KC_FFT_DEC_PACKED, KC_COUNT
 };
 struct ProfScope {
   int cls;
@@ -582,6 +583,20 @@ void k_step_tail_batch(uint64_t *up, const uint64_t *uhat, unsigned lvl, unsigne
 void k_rows_fold_add_batch(uint64_t *y, const uint64_t *R, unsigned nl, unsigned cnt);
 // up [cnt][2][lvl-1][n] <- the limbs below lvl - 1 of uhat [cnt][2][lvl][n] - (up + R)
 void k_rows_fold_tail_batch(uint64_t *up, const uint64_t *R, const uint64_t *uhat, unsigned lvl, unsigned cnt);
+// he_enc_pk_packed_batch / he_dec_dcd_packed_batch (gpqhe_ext_packed_batch.h):
+// S = P s slots, entry k of loop p at packed slot k P + p.
+// v [cnt][S] complex values (device) <- z [cnt][P][width] (device): v[c][k P + p]
+// = z[c][p][k] for k < width, else 0 (packed_batch.hip)
+void k_pack_enc_gather(double *v, const double *z, unsigned S, unsigned P, unsigned width, unsigned cnt);
+// out [cnt][P][rows] complex values (device) <- z [cnt][S] (device): out[c][p][k]
+// = z[c][k P + p] (packed_batch.hip)
+void k_pack_dcd_gather(double *out, const double *z, unsigned S, unsigned P, unsigned rows, unsigned cnt);
+// k_decode / k_fold_decode (S <= GPQHE_DCD_ONEPASS) whose epilogue writes that
+// compact form instead: z [P][rows] of one ciphertext, [cnt][P][rows] of a chunk
+void k_decode_packed(double *z, const uint64_t *coef, unsigned nl, unsigned S, double scale, unsigned P,
+                     unsigned rows);
+void k_fold_decode_packed(double *z, uint64_t *D, const uint64_t *F, unsigned nl, unsigned S, double scale,
+                          unsigned cnt, unsigned P, unsigned rows);
 void tables_upload();
 void tables_prewarm();
 void tables_free();

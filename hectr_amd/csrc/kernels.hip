@@ -52,7 +52,8 @@ static const char *kc_names[KC_COUNT] = {
   "bsgs_inner_kernel", "bsgs_sum_kernel", "bsgs_inner_batch_kernel", "bsgs_sum_batch_kernel",
   "fft_enc_batch_kernel", "enc_sample_batch_kernel", "enc_combine_batch_kernel", "dec_fold_kernel",
   "fold_dcd_kernel", "dec_batch_kernel", "step_diff_batch_kernel", "step_tail_batch_kernel",
-  "rows_fold_add_batch_kernel", "rows_fold_tail_batch_kernel"};
+  "rows_fold_add_batch_kernel", "rows_fold_tail_batch_kernel", "pack_enc_gather_kernel", "pack_dcd_gather_kernel",
+  "fold_dcd_packed_kernel", "fft_dec_lds_packed_kernel"};
 
 struct ProfEntry {
   int cls;
@@ -1429,11 +1430,15 @@ __device__ double dcd_crt_center(const uint64_t *c, unsigned k, unsigned nl, uns
 }
 
 // One chunk of len0 elements at base: lift into sh, stages 2 .. len0, store.
-template <int NLM>
+// PK (the one chunk of s <= FFT_LDS slots, base 0): the store is the packed
+// decode's instead -- s = P loops' slots, entry k of loop p at slot k P + p;
+// v [P][rows] <- the first rows entries of every loop, the others skipped
+// (the strided side on the LDS read, the store coalesced).
+template <int NLM, bool PK = false>
 __device__ __forceinline__ void dcd_chunk(double2 *sh, double2 *v, unsigned base, const uint64_t *c, unsigned nl,
                                           unsigned logn, unsigned s, unsigned logs, unsigned len0, double scale,
                                           const ModConst *mc, const uint64_t *ginv, unsigned ld, const double2 *ksi,
-                                          const unsigned *rot)
+                                          const unsigned *rot, unsigned P = 1, unsigned rows = 0)
 {
   const unsigned M = 4 * s, gap = (1u << logn) / (2 * s);
   for (unsigned e = threadIdx.x; e < len0; e += blockDim.x) {
@@ -1451,8 +1456,15 @@ __device__ __forceinline__ void dcd_chunk(double2 *sh, double2 *v, unsigned base
     }
     __syncthreads();
   }
-  for (unsigned e = threadIdx.x; e < len0; e += blockDim.x)
-    v[base + e] = sh[e];
+  if constexpr (PK) {
+    for (unsigned o = threadIdx.x; o < P * rows; o += blockDim.x) {
+      const unsigned p = o / rows, k = o - p * rows;
+      v[o] = sh[k * P + p];
+    }
+  } else {
+    for (unsigned e = threadIdx.x; e < len0; e += blockDim.x)
+      v[base + e] = sh[e];
+  }
 }
 
 template <int NLM>
@@ -1463,6 +1475,19 @@ __global__ void __launch_bounds__(512) fft_dec_lds_kernel(double2 *v, const uint
 {
   __shared__ double2 sh[FFT_LDS];
   dcd_chunk<NLM>(sh, v, blockIdx.x * len0, c, nl, logn, s, logs, len0, scale, mc, ginv, ld, ksi, rot);
+}
+
+// The decoder of s <= FFT_LDS slots (one workgroup) with the packed store:
+// z [P][rows] (he_dec_dcd_packed_batch).
+template <int NLM>
+__global__ void __launch_bounds__(512) fft_dec_lds_packed_kernel(double2 *z, const uint64_t *c, unsigned nl,
+                                                                 unsigned logn, unsigned s, unsigned logs,
+                                                                 double scale, const ModConst *mc,
+                                                                 const uint64_t *ginv, unsigned ld, const double2 *ksi,
+                                                                 const unsigned *rot, unsigned P, unsigned rows)
+{
+  __shared__ double2 sh[FFT_LDS];
+  dcd_chunk<NLM, true>(sh, z, 0, c, nl, logn, s, logs, s, scale, mc, ginv, ld, ksi, rot, P, rows);
 }
 
 __global__ void fft_dec_stage_kernel(double2 *v, unsigned s, unsigned len, const double2 *ksi, const unsigned *rot)
@@ -1517,6 +1542,33 @@ void k_decode(double *z, const uint64_t *coef, unsigned nl, unsigned s, double s
   for (unsigned len = 2 * len0; len <= s; len <<= 1)
     hipLaunchKernelGGL(fft_dec_stage_kernel, dim3((s / 2 + TPB - 1) / TPB), dim3(TPB), 0, G.stream, v, s, len,
                        T.ksi, T.rot);
+  HIP_CHECK(hipGetLastError());
+}
+
+void k_decode_packed(double *z, const uint64_t *coef, unsigned nl, unsigned S, double scale, unsigned P, unsigned rows)
+{
+  const FftDev &T = fft_dev(S);
+  if (nl < 1 || nl > G.L || S > FFT_LDS || !P || S % P || !rows || rows > S / P)
+    gpqhe_die("k_decode_packed: %u limbs, %u slots, %u loops, %u rows", nl, S, P, rows);
+  garner_table();
+  const unsigned logs = (unsigned)__builtin_ctz(S);
+  const dim3 grid(1), block(std::min(512u, std::max(64u, S / 2)));
+  // the 2 S coefficients read over nl limbs, P rows values written
+  ProfScope ps(KC_FFT_DEC_PACKED, 16.0 * nl * S + 16.0 * P * rows);
+#define GPQHE_DCDP(NLM)                                                                                             \
+  hipLaunchKernelGGL(fft_dec_lds_packed_kernel<NLM>, grid, block, 0, G.stream, (double2 *)z, coef, nl, G.logn, S, \
+                     logs, scale, G.dev.mc, g_ginv, G.L, T.ksi, T.rot, P, rows)
+  if (nl <= 2)
+    GPQHE_DCDP(2);
+  else if (nl <= 4)
+    GPQHE_DCDP(4);
+  else if (nl <= 8)
+    GPQHE_DCDP(8);
+  else if (nl <= 16)
+    GPQHE_DCDP(16);
+  else
+    GPQHE_DCDP(GPQHE_MAXMOD);
+#undef GPQHE_DCDP
   HIP_CHECK(hipGetLastError());
 }
 
@@ -4474,14 +4526,14 @@ void k_dec_fold(uint64_t *F, const uint64_t *y, const uint64_t *sk, unsigned s, 
 // inverse that are left), n^-1, out to D; then dcd_chunk on D as a ring of
 // m coefficients (gap 1), which the workgroup reads after a barrier as
 // inv_dcd_kernel does.
-template <int NLM>
-__global__ void __launch_bounds__(512) fold_dcd_kernel(double2 *z, uint64_t *D, const uint64_t *F, unsigned nl,
-                                                        unsigned logm, unsigned s, unsigned logs, double scale,
-                                                        const uint64_t *itw, const uint64_t *itwp, unsigned logn,
-                                                        const ModConst *mcs, const uint64_t *ginv, unsigned ld,
-                                                        const double2 *ksi, const unsigned *rot)
+// PK: the packed store of dcd_chunk, z [cnt][P][rows].
+template <int NLM, bool PK>
+__device__ __forceinline__ void fold_dcd_body(uint64_t *lds, double2 *z, uint64_t *D, const uint64_t *F, unsigned nl,
+                                              unsigned logm, unsigned s, unsigned logs, double scale,
+                                              const uint64_t *itw, const uint64_t *itwp, unsigned logn,
+                                              const ModConst *mcs, const uint64_t *ginv, unsigned ld,
+                                              const double2 *ksi, const unsigned *rot, unsigned P, unsigned rows)
 {
-  __shared__ __attribute__((aligned(16))) uint64_t lds[2 * FFT_LDS];
   const unsigned m = 1u << logm;
   const uint64_t *Fc = F + (size_t)blockIdx.x * nl * m;
   uint64_t *Dc = D + (size_t)blockIdx.x * nl * m;
@@ -4506,8 +4558,31 @@ __global__ void __launch_bounds__(512) fold_dcd_kernel(double2 *z, uint64_t *D, 
       Dc[(size_t)l * m + e] = mul_shoup(lds[e], mc.ninv, mc.ninvp, mc.q);
   }
   __syncthreads();
-  dcd_chunk<NLM>((double2 *)lds, z + (size_t)blockIdx.x * s, 0, Dc, nl, logm, s, logs, s, scale, mcs, ginv, ld, ksi,
-                 rot);
+  dcd_chunk<NLM, PK>((double2 *)lds, z + (size_t)blockIdx.x * (PK ? P * rows : s), 0, Dc, nl, logm, s, logs, s, scale,
+                     mcs, ginv, ld, ksi, rot, P, rows);
+}
+
+template <int NLM>
+__global__ void __launch_bounds__(512) fold_dcd_kernel(double2 *z, uint64_t *D, const uint64_t *F, unsigned nl,
+                                                        unsigned logm, unsigned s, unsigned logs, double scale,
+                                                        const uint64_t *itw, const uint64_t *itwp, unsigned logn,
+                                                        const ModConst *mcs, const uint64_t *ginv, unsigned ld,
+                                                        const double2 *ksi, const unsigned *rot)
+{
+  __shared__ __attribute__((aligned(16))) uint64_t lds[2 * FFT_LDS];
+  fold_dcd_body<NLM, false>(lds, z, D, F, nl, logm, s, logs, scale, itw, itwp, logn, mcs, ginv, ld, ksi, rot, 1, 0);
+}
+
+template <int NLM>
+__global__ void __launch_bounds__(512) fold_dcd_packed_kernel(double2 *z, uint64_t *D, const uint64_t *F, unsigned nl,
+                                                               unsigned logm, unsigned s, unsigned logs, double scale,
+                                                               const uint64_t *itw, const uint64_t *itwp,
+                                                               unsigned logn, const ModConst *mcs,
+                                                               const uint64_t *ginv, unsigned ld, const double2 *ksi,
+                                                               const unsigned *rot, unsigned P, unsigned rows)
+{
+  __shared__ __attribute__((aligned(16))) uint64_t lds[2 * FFT_LDS];
+  fold_dcd_body<NLM, true>(lds, z, D, F, nl, logm, s, logs, scale, itw, itwp, logn, mcs, ginv, ld, ksi, rot, P, rows);
 }
 
 void k_fold_decode(double *z, uint64_t *D, const uint64_t *F, unsigned nl, unsigned s, double scale, unsigned cnt)
@@ -4533,6 +4608,33 @@ void k_fold_decode(double *z, uint64_t *D, const uint64_t *F, unsigned nl, unsig
   else
     GPQHE_FDCD(GPQHE_MAXMOD);
 #undef GPQHE_FDCD
+  HIP_CHECK(hipGetLastError());
+}
+
+void k_fold_decode_packed(double *z, uint64_t *D, const uint64_t *F, unsigned nl, unsigned S, double scale,
+                          unsigned cnt, unsigned P, unsigned rows)
+{
+  const FftDev &T = fft_dev(S);
+  if (nl < 1 || nl > G.L || S > FFT_LDS || 2 * S >= G.n || !P || S % P || !rows || rows > S / P)
+    gpqhe_die("k_fold_decode_packed: n = %u, %u limbs, %u slots, %u loops, %u rows", G.n, nl, S, P, rows);
+  garner_table();
+  const unsigned logs = (unsigned)__builtin_ctz(S);
+  const dim3 grid(cnt), block(std::min(512u, std::max(64u, S)));
+  ProfScope ps(KC_FOLD_DCD_PACKED, (32.0 * nl * S + 16.0 * P * rows) * cnt);
+#define GPQHE_FDCDP(NLM)                                                                                          \
+  hipLaunchKernelGGL(fold_dcd_packed_kernel<NLM>, grid, block, 0, G.stream, (double2 *)z, D, F, nl, logs + 1, S, \
+                     logs, scale, G.dev.itw, G.dev.itwp, G.logn, G.dev.mc, g_ginv, G.L, T.ksi, T.rot, P, rows)
+  if (nl <= 2)
+    GPQHE_FDCDP(2);
+  else if (nl <= 4)
+    GPQHE_FDCDP(4);
+  else if (nl <= 8)
+    GPQHE_FDCDP(8);
+  else if (nl <= 16)
+    GPQHE_FDCDP(16);
+  else
+    GPQHE_FDCDP(GPQHE_MAXMOD);
+#undef GPQHE_FDCDP
   HIP_CHECK(hipGetLastError());
 }
 

@@ -490,3 +490,86 @@ class BatchedEncryptedRegulator:
         e.free(self.sk)
         e.free_evks(self.rk)
         self.x = self.up = None
+
+
+class PackedEncryptedRegulator:
+    """ctr_hempc for many control loops per ciphertext (include/gpqhe_ext_packed_batch.h):
+    a context of slots_total slots carries P = slots_total / s loops of s =
+    problem.slots slots, entry k of loop p at slot k P + p, so len(problems)
+    loops go into ceil(len / P) ciphertexts, the last one padded with zero
+    loops.  One he_enc_pk_packed_batch of the 4 count vectors,
+    he_hempc_step_packed_batch on the he_genrk_packed(s, rows) keys,
+    he_dec_dcd_packed_batch.  Loop p uses its own problem's MA / MB (nmat = P;
+    loop p of every ciphertext the same, so with several ciphertexts the
+    problems P apart must share their gains), or one shared pair (nmat = 1)
+    when all problems are one object.  __call__ is BatchedEncryptedRegulator's:
+    [len(problems)][.] arrays in, u [len(problems)][nu] out."""
+
+    def __init__(self, engine, problems, slots_total, rows=None, seed=None, logn=12, logq=109, log_delta=50,
+                 init=True):
+        import torch
+        pb = problems[0]
+        s = pb.slots
+        self.e, self.problems, self.s, self.S = engine, list(problems), s, slots_total
+        self.rows = pb.nu if rows is None else rows
+        assert all(q.slots == s and (q.nx, q.nu) == (pb.nx, pb.nu) for q in problems)
+        assert slots_total % s == 0 and pb.nu <= self.rows <= s
+        self.P = P = slots_total // s
+        self.nloops = len(problems)
+        self.count = count = -(-self.nloops // P)
+        if init:
+            engine.init(logn, logq, slots_total, log_delta)
+        assert engine.slots == slots_total
+        if seed is not None:
+            engine.set_seed(seed)
+        self.pk, self.sk = engine.pk(), engine.sk()
+        self.rk = engine.evks(slots_total)
+        engine.keypair(self.pk, self.sk)
+        engine.genrk_packed(self.rk, self.sk, s, self.rows)
+        self.lvl, self.scale = engine.L, engine.info.delta
+        self.cw = 2 * self.lvl * engine.n                  # words of one input ciphertext
+        self.x = torch.zeros(4 * count * self.cw, dtype=torch.int64, device="cuda")
+        self.up = torch.zeros(count * 2 * (self.lvl - 1) * engine.n, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        self.width = max(pb.nx, pb.nu)
+        r = self.rows
+        if all(q is pb for q in problems):
+            self.nmat = 1
+            self.MAz = d2z_matrix(pb.MA, s)[:r].ravel()
+            self.MBz = d2z_matrix(pb.MB, s)[:r].ravel()
+        else:
+            self.nmat = P
+            owner = [None] * P                             # loop p of every ciphertext: one pair of gains
+            for i, q in enumerate(problems):
+                o = owner[i % P]
+                assert o is None or o is q or (np.array_equal(o.MA, q.MA) and np.array_equal(o.MB, q.MB)), \
+                    "problems P apart share a loop position and must share their gains"
+                owner[i % P] = o or q
+            zero = np.zeros((r, s), dtype=np.complex128)
+            self.MAz = np.stack([d2z_matrix(q.MA, s)[:r] if q else zero for q in owner]).ravel()
+            self.MBz = np.stack([d2z_matrix(q.MB, s)[:r] if q else zero for q in owner]).ravel()
+        self.timings = []
+
+    def __call__(self, xhat, uhat, xr, ur):
+        e, cnt, P, w = self.e, self.count, self.P, self.width
+        t0 = time.perf_counter()
+        zs = np.zeros((4, cnt * P, w), dtype=np.complex128)
+        for b, v in enumerate((xhat, xr, uhat, ur)):
+            v = np.asarray(v, dtype=np.float64).reshape(self.nloops, -1)
+            zs[b, :self.nloops, :v.shape[1]] = v
+        e.enc_pk_packed_batch(self.x.data_ptr(), zs.reshape(4 * cnt, P, w), self.pk, self.s, w, self.scale, self.lvl)
+        part = [self.x.data_ptr() + 8 * b * cnt * self.cw for b in range(4)]
+        e.hempc_step_packed_batch(self.up.data_ptr(), self.MAz, self.MBz, part[0], part[1], part[2], part[3], cnt,
+                                  self.lvl, self.rk, self.s, self.rows, self.nmat)
+        uz = e.dec_dcd_packed_batch(self.up.data_ptr(), cnt, self.lvl - 1, self.scale, self.sk, self.s, self.rows)
+        assert np.all(uz.imag < HECTR_SMALL), "imaginary part too large (src/ctr.c:493-494)"
+        self.timings.append(time.perf_counter() - t0)
+        return uz.real.reshape(cnt * P, self.rows)[:self.nloops, :self.problems[0].nu].copy()
+
+    def close(self):
+        e = self.e
+        e.sync()
+        e.free(self.pk)
+        e.free(self.sk)
+        e.free_evks(self.rk)
+        self.x = self.up = None

@@ -186,6 +186,17 @@ PRODUCT_EXT_ROWS_BATCH = {
     "he_hempc_step_rows_batch": (None, [VP, VP, VP, VP, VP, VP, VP, C.c_size_t, C.c_uint, OBJ, C.c_uint]),
 }
 
+#: include/gpqhe_ext_packed_batch.h (part of gpqhe_ext_batch.h): many control
+#: loops per ciphertext, product only, bound like PRODUCT_EXT
+PRODUCT_EXT_PACKED_BATCH = {
+    "he_genrk_packed": (None, [OBJ, OBJ, C.c_uint, C.c_uint]),
+    "he_gemv2_packed_batch": (None, [VP, VP, VP, VP, VP, C.c_size_t, C.c_uint, OBJ, C.c_uint, C.c_uint, C.c_uint]),
+    "he_hempc_step_packed_batch": (None, [VP, VP, VP, VP, VP, VP, VP, C.c_size_t, C.c_uint, OBJ, C.c_uint, C.c_uint,
+                                          C.c_uint]),
+    "he_enc_pk_packed_batch": (None, [VP, VP, C.c_size_t, C.c_uint, C.c_uint, C.c_double, C.c_uint, OBJ]),
+    "he_dec_dcd_packed_batch": (None, [VP, VP, C.c_size_t, C.c_uint, C.c_double, C.c_uint, C.c_uint, OBJ]),
+}
+
 
 def _cplx(z) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(z, dtype=np.complex128))
@@ -208,7 +219,8 @@ class Engine:
             f.restype = res
             f.argtypes = args
         for sym, (res, args) in {**PRODUCT_EXT, **PRODUCT_EXT_BATCH, **PRODUCT_EXT_IO_BATCH,
-                                 **PRODUCT_EXT_STEP_BATCH, **PRODUCT_EXT_ROWS_BATCH}.items():
+                                 **PRODUCT_EXT_STEP_BATCH, **PRODUCT_EXT_ROWS_BATCH,
+                                 **PRODUCT_EXT_PACKED_BATCH}.items():
             if hasattr(self.lib, sym):  # not the oracle, nor an older library under GPQHE_LIB
                 f = getattr(self.lib, sym)
                 f.restype = res
@@ -403,6 +415,50 @@ class Engine:
         Ma, Mb = _cplx(Ma), _cplx(Mb)
         self._ext("he_hempc_step_rows_batch")(up_ptr, Ma.ctypes.data, Mb.ctypes.data, xhat_ptr, xr_ptr, uhat_ptr,
                                               ur_ptr, count, nlimbs, rk, rows)
+
+    def genrk_packed(self, rk, sk, s, rows):
+        """The rotation keys the packed row-folded product (loops of s slots,
+        `rows` leading rows) can need, into rk[slots] (include/gpqhe_ext_packed_batch.h)."""
+        self._ext("he_genrk_packed")(rk, C.byref(sk), s, rows)
+
+    def gemv2_packed_batch(self, y_ptr, Ma, xa_ptr, Mb, xb_ptr, count, nlimbs, rk, s, rows, nmat=1):
+        """The leading `rows` rows of Ma_p xa_p + Mb_p xb_p for each of the
+        P = slots / s loops a ciphertext carries (entry k of loop p at slot
+        k P + p); Ma, Mb [nmat][rows][s], nmat 1 or P; xa_ptr, xb_ptr
+        [count][2][nlimbs][n] -> y_ptr [count][2][nlimbs-1][n], device memory
+        (include/gpqhe_ext_packed_batch.h)."""
+        f = self._ext("he_gemv2_packed_batch")
+        Ma, Mb = _cplx(Ma), _cplx(Mb)
+        assert Ma.size >= nmat * rows * s and Mb.size >= nmat * rows * s
+        f(y_ptr, Ma.ctypes.data, xa_ptr, Mb.ctypes.data, xb_ptr, count, nlimbs, rk,
+          s, rows, nmat)
+
+    def hempc_step_packed_batch(self, up_ptr, Ma, Mb, xhat_ptr, xr_ptr, uhat_ptr, ur_ptr, count, nlimbs, rk, s, rows,
+                                nmat=1):
+        """ctr_hempc for the P = slots / s loops of each of `count` ciphertexts,
+        its product the packed row-folded one; four inputs [count][2][nlimbs][n]
+        -> up_ptr [count][2][nlimbs-1][n], device memory
+        (include/gpqhe_ext_packed_batch.h)."""
+        f = self._ext("he_hempc_step_packed_batch")
+        Ma, Mb = _cplx(Ma), _cplx(Mb)
+        assert Ma.size >= nmat * rows * s and Mb.size >= nmat * rows * s
+        f(up_ptr, Ma.ctypes.data, Mb.ctypes.data, xhat_ptr, xr_ptr, uhat_ptr, ur_ptr, count, nlimbs, rk, s, rows, nmat)
+
+    def enc_pk_packed_batch(self, x_ptr, zs, pk, s, width, scale, nlimbs):
+        """he_ecd_ex + he_enc_pk of zs [count][slots / s][width] (loop-major,
+        entries past width zero) into device memory x_ptr [count][2][nlimbs][n]
+        (include/gpqhe_ext_packed_batch.h)."""
+        f = self._ext("he_enc_pk_packed_batch")
+        zs = _cplx(zs).reshape(-1, self.slots // s, width)
+        f(x_ptr, zs.ctypes.data, zs.shape[0], s, width, scale, nlimbs, C.byref(pk))
+
+    def dec_dcd_packed_batch(self, y_ptr, count, nlimbs, scale, sk, s, rows):
+        """he_dec + he_dcd_ex of `count` ciphertexts in device memory, the first
+        `rows` entries of every loop: a complex128 array [count][slots / s][rows]."""
+        f = self._ext("he_dec_dcd_packed_batch")
+        z = np.zeros((count, self.slots // s, rows), dtype=np.complex128)
+        f(z.ctypes.data, y_ptr, count, nlimbs, scale, s, rows, C.byref(sk))
+        return z
 
     def enc_pk_batch(self, x_ptr, zs, pk, slots, scale, nlimbs):
         """he_ecd_ex + he_enc_pk of the rows of zs [count][slots] into device

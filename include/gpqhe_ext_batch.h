@@ -35,5 +35,7 @@ void he_gemv_bsgs_batch(uint64_t *y, const gpqhe_complex_t M[], const uint64_t *
 #include "gpqhe_ext_io_batch.h"
 #include "gpqhe_ext_step_batch.h"
 #include "gpqhe_ext_rows_batch.h"
+/* many control loops per ciphertext: the row-folded step at a slot stride */
+#include "gpqhe_ext_packed_batch.h"
 
 #endif /* GPQHE_EXT_BATCH_H */
