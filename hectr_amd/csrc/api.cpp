@@ -37,9 +37,7 @@ static void flush_ew();
 static void fold_cache_trim();
 static unsigned env_u(const char *name, unsigned dflt);
 void gemv_cache_clear();
-static void bsgs_cache_clear();
-static void bsgs2_cache_clear();
-static void rows_cache_clear();
+static void plan_caches_clear();
 
 void *pool_alloc(size_t bytes)
 {
@@ -1129,9 +1127,7 @@ extern "C" void hectx_exit(void)
   g_sd_off = false;
   k_prof_release();
   gemv_cache_clear();
-  bsgs_cache_clear();
-  bsgs2_cache_clear();
-  rows_cache_clear();
+  plan_caches_clear();
   fold_cache_clear();
   g_key_gen++;
   tables_free();
@@ -1347,14 +1343,26 @@ static void gen_rot_key(he_evk_t *evk, uint64_t g, const poly_mpi_t *sk)
   gen_evk(evk, sp.p, sk, (uint32_t)g);
 }
 
-extern "C" void he_genrk(he_evk_t rk[], const poly_mpi_t *sk)
+// rk[r] <- the key of every rotation r in [1, slots) that `want` selects, in
+// ascending r (the keys' stream numbers follow that order); the others freed.
+template <class Want>
+static void gen_rot_keys(he_evk_t rk[], const poly_mpi_t *sk, Want want)
 {
-  check_ctx();
   if (rk[0].data)
     obj_free(&rk[0]);
   rk[0].galois = 1;
-  for (unsigned r = 1; r < G.slots; r++)
-    gen_rot_key(&rk[r], galois_of_rot(r), sk);
+  for (unsigned r = 1; r < G.slots; r++) {
+    if (want(r))
+      gen_rot_key(&rk[r], galois_of_rot(r), sk);
+    else if (rk[r].data)
+      he_free_evk(&rk[r]);
+  }
+}
+
+extern "C" void he_genrk(he_evk_t rk[], const poly_mpi_t *sk)
+{
+  check_ctx();
+  gen_rot_keys(rk, sk, [](unsigned) { return true; });
 }
 
 extern "C" void he_genrot(he_evk_t *evk, unsigned int rot, const poly_mpi_t *sk)
@@ -2903,34 +2911,130 @@ extern "C" void he_gemv(he_ct_t *y, const gpqhe_complex_t M[], const he_ct_t *x,
 // Non-queued: it takes no part in the small-N step's queues and speculation,
 // and he_gemv takes none of this code.
 //
-// The encoded diagonals live in a cache of their own (g_bsgs), keyed by the
-// bytes of M, the level and g, least recently used first out, bounded by
-// diag_cache_cap().  An entry owns its device blocks; nothing outside this
-// section keeps a pointer into one across calls, and a call holds its entry
-// only until it returns (nothing inside a call evicts).
+// The encoded diagonals live in a plan cache (PlanCache), keyed by a header of
+// integers and the bytes of the matrices, least recently used first out,
+// bounded by diag_cache_cap().  There are three instances, each bounded on its
+// own, so what one kind of call finds does not depend on calls of another:
+//   g_bsgs   (s, lvl, g), M                    he_gemv_bsgs, he_gemv_bsgs_batch
+//   g_bsgs2  (s, lvl, g), the ordered (Ma, Mb) he_gemv2_bsgs_batch, he_hempc_step_batch
+//   g_rows   (s, lvl, rows, sl, nmat), the leading rows of (Ma, Mb)
+//                                              the row-folded and packed forms
+// An entry owns its device blocks; nothing outside this section keeps a pointer
+// into one across calls, and a call holds its entry only until it returns
+// (nothing inside a call evicts).
 // ===========================================================================
-struct BsgsPlan {
-  std::vector<double> M;        // the matrix it was made from (compared in place on a lookup)
-  unsigned s = 0, lvl = 0, g = 0;
+// One operand's host lists.
+struct BsgsOp {
   std::vector<unsigned> ds;     // the non-zero diagonals, ascending: pts order
   std::vector<unsigned> baby;   // the baby rotations they use, ascending: slot order of B
-  std::vector<unsigned> giant;  // the giant steps they use, ascending: row order of tab and U
-  std::vector<int> tab;         // [giant][baby] -> index into pts, -1: none
-  uint64_t *pts = nullptr;      // [ds.size()][lvl][n]
+  std::vector<unsigned> giant;  // the giant steps they use, ascending: row order of tab
+  std::vector<int> tab;         // [giant][baby] -> index into the operand's diagonals, -1: none
+};
+
+// The plan of y = Ma xa (+ Mb xb): operand b is empty for the single product.
+struct BsgsPlan {
+  std::vector<unsigned> hdr;    // the key: the header and the matrices it was made
+  std::vector<double> Ma, Mb;   // from (compared in place on a lookup)
+  BsgsOp a, b;
+  std::vector<unsigned> giant;  // the union of their giant steps, ascending: row order of tab and U
+  std::vector<int> tab;         // [giant][baby slots of a | baby slots of b] -> index into pts, -1: none
+  uint64_t *pts = nullptr;      // [a.ds.size() + b.ds.size()][lvl][n]: a's diagonals, then b's
   int *tab_dev = nullptr;
   size_t bytes = 0;
+  unsigned ndiag() const { return (unsigned)(a.ds.size() + b.ds.size()); }
 };
-static std::list<BsgsPlan> g_bsgs;
-static size_t g_bsgs_bytes = 0;
 
-static void bsgs_cache_clear()
-{
-  for (BsgsPlan &p : g_bsgs) {
-    pool_free(p.pts);
-    pool_free(p.tab_dev);
+// What keeps a plan that is not in the cache alive for one call.
+struct PlanHold {
+  BsgsPlan tmp;
+  std::unique_ptr<Ws> pts, tab;
+};
+
+struct PlanCache {
+  std::list<BsgsPlan> plans;  // most recently used first (a list: a running call's entry stays where it is)
+  size_t bytes = 0;
+
+  void clear()
+  {
+    for (BsgsPlan &p : plans) {
+      pool_free(p.pts);
+      pool_free(p.tab_dev);
+    }
+    plans.clear();
+    bytes = 0;
   }
-  g_bsgs.clear();
-  g_bsgs_bytes = 0;
+
+  // The plan of (hdr, Ma, Mb) at level lvl, mwords doubles per matrix (Mb null:
+  // one matrix): cached, or (a set larger than the cache, or no diagonal at
+  // all) in the holder.  plan(p) fills p.a and p.b on the host, encode(p, pts)
+  // writes their diagonals' limbs.  One compare of the matrices per call; every
+  // eviction happens here, before the call's first launch.
+  template <class Plan, class Encode>
+  const BsgsPlan *get(PlanHold &h, const std::vector<unsigned> &hdr, unsigned lvl, const double *Ma, const double *Mb,
+                      size_t mwords, Plan plan, Encode encode)
+  {
+    for (auto it = plans.begin(); it != plans.end(); ++it)
+      if (it->hdr == hdr && !memcmp(it->Ma.data(), Ma, mwords * 8) && (!Mb || !memcmp(it->Mb.data(), Mb, mwords * 8))) {
+        plans.splice(plans.begin(), plans, it);
+        return &plans.front();
+      }
+    BsgsPlan &tmp = h.tmp;
+    plan(tmp);
+    const BsgsOp &a = tmp.a, &b = tmp.b;
+    if (!tmp.ndiag())
+      return &tmp;  // no diagonal: no blocks
+    std::set_union(a.giant.begin(), a.giant.end(), b.giant.begin(), b.giant.end(), std::back_inserter(tmp.giant));
+    const size_t na = a.baby.size(), nb = b.baby.size(), gs = na + nb;
+    tmp.tab.assign(tmp.giant.size() * gs, -1);
+    for (size_t r = 0, ja = 0, jb = 0; r < tmp.giant.size(); r++) {
+      if (ja < a.giant.size() && a.giant[ja] == tmp.giant[r]) {
+        for (size_t i = 0; i < na; i++)
+          tmp.tab[r * gs + i] = a.tab[ja * na + i];
+        ja++;
+      }
+      if (jb < b.giant.size() && b.giant[jb] == tmp.giant[r]) {
+        for (size_t i = 0; i < nb; i++)
+          if (b.tab[jb * nb + i] >= 0)
+            tmp.tab[r * gs + na + i] = (int)a.ds.size() + b.tab[jb * nb + i];
+        jb++;
+      }
+    }
+    const size_t pw = (size_t)lvl * G.n, tabw = (tmp.tab.size() * sizeof(int) + 7) / 8;
+    tmp.bytes = tmp.ndiag() * pw * 8;
+    if (tmp.bytes > diag_cache_cap()) {
+      h.pts.reset(new Ws(tmp.ndiag() * pw));
+      h.tab.reset(new Ws(tabw));
+      tmp.pts = h.pts->p;
+      tmp.tab_dev = (int *)h.tab->p;
+    } else {
+      while (!plans.empty() && bytes + tmp.bytes > diag_cache_cap()) {
+        pool_free(plans.back().pts);
+        pool_free(plans.back().tab_dev);
+        bytes -= plans.back().bytes;
+        plans.pop_back();
+      }
+      tmp.pts = (uint64_t *)pool_alloc(tmp.bytes);
+      tmp.tab_dev = (int *)pool_alloc(tabw * 8);
+    }
+    encode(tmp, tmp.pts);
+    upload(tmp.tab_dev, tmp.tab.data(), tmp.tab.size() * sizeof(int));
+    if (h.pts)
+      return &tmp;
+    tmp.hdr = hdr;  // the owned copies: made on a miss only
+    tmp.Ma.assign(Ma, Ma + mwords);
+    if (Mb)
+      tmp.Mb.assign(Mb, Mb + mwords);
+    bytes += tmp.bytes;
+    plans.push_front(std::move(tmp));
+    return &plans.front();
+  }
+};
+static PlanCache g_bsgs, g_bsgs2, g_rows;
+
+static void plan_caches_clear()
+{
+  for (PlanCache *c : {&g_bsgs, &g_bsgs2, &g_rows})
+    c->clear();
 }
 
 static unsigned bsgs_default_g()
@@ -2942,7 +3046,7 @@ static unsigned bsgs_default_g()
 }
 
 // Which diagonals, baby rotations and giant steps M uses (host only).
-static void bsgs_plan(BsgsPlan &p, const double *Md, unsigned g)
+static void bsgs_plan(BsgsOp &p, const double *Md, unsigned g)
 {
   const unsigned s = G.slots, ng = (s + g - 1) / g;
   std::vector<char> ub(g, 0), uj(ng, 0);
@@ -2968,7 +3072,7 @@ static void bsgs_plan(BsgsPlan &p, const double *Md, unsigned g)
 }
 
 // pts <- P_j,i of every non-zero diagonal d = j g + i, in p.ds order.
-static void bsgs_encode(const BsgsPlan &p, const double *Md, unsigned lvl, unsigned g, uint64_t *pts)
+static void bsgs_encode(const BsgsOp &p, const double *Md, unsigned lvl, unsigned g, uint64_t *pts)
 {
   const unsigned s = G.slots;
   unsigned mods[GPQHE_MAXMOD];
@@ -3014,93 +3118,45 @@ extern "C" void he_genrk_bsgs(he_evk_t rk[], const poly_mpi_t *sk, unsigned int 
     g = bsgs_default_g();
   if (g > s)
     gpqhe_die("he_genrk_bsgs: g = %u > slots = %u", g, s);
-  if (rk[0].data)
-    obj_free(&rk[0]);
-  rk[0].galois = 1;
-  for (unsigned r = 1; r < s; r++) {
-    if (r < g || r % g == 0)
-      gen_rot_key(&rk[r], galois_of_rot(r), sk);
-    else if (rk[r].data)
-      he_free_evk(&rk[r]);
-  }
+  gen_rot_keys(rk, sk, [g](unsigned r) { return r < g || r % g == 0; });
 }
 
 // ---------------------------------------------------------------------------
-// The stages of a BSGS product, shared by he_gemv_bsgs and he_gemv_bsgs_batch
+// The stages of a BSGS product, shared by he_gemv_bsgs and the batch products
 // (include/gpqhe_ext_batch.h).  A stage writes its slots (baby slots, rotated
 // giant steps) `stride` words apart: 2 lvl n for the single call's packed
 // buffers, cnt 2 lvl n for a chunk's slot-major ones.
 // ---------------------------------------------------------------------------
-// What keeps a plan that is not in the cache alive for one call.
-struct BsgsPlanHold {
-  BsgsPlan tmp;
-  std::unique_ptr<Ws> pts, tab;
-};
-
-// The encoded diagonals of (M, lvl, g): cached, or (a set larger than the
-// cache, or the zero matrix) in the holder.  One compare of M per call; every
-// eviction happens here, before the call's first launch.
-static const BsgsPlan *bsgs_plan_get(BsgsPlanHold &h, const double *Md, unsigned lvl, unsigned g)
+// The plan of one matrix: (M, lvl, g) in g_bsgs.
+static const BsgsPlan *bsgs_plan_get(PlanHold &h, const double *Md, unsigned lvl, unsigned g)
 {
   const unsigned s = G.slots;
-  const size_t pw = (size_t)lvl * G.n, mwords = 2 * (size_t)s * s;
-  for (auto it = g_bsgs.begin(); it != g_bsgs.end(); ++it)
-    if (it->s == s && it->lvl == lvl && it->g == g && !memcmp(it->M.data(), Md, mwords * 8)) {
-      g_bsgs.splice(g_bsgs.begin(), g_bsgs, it);
-      return &g_bsgs.front();
-    }
-  BsgsPlan &tmp = h.tmp;
-  bsgs_plan(tmp, Md, g);
-  const size_t tabw = (tmp.tab.size() * sizeof(int) + 7) / 8;
-  tmp.bytes = tmp.ds.size() * pw * 8;
-  if (tmp.bytes > diag_cache_cap()) {
-    h.pts.reset(new Ws(tmp.ds.size() * pw));
-    h.tab.reset(new Ws(tabw));
-    tmp.pts = h.pts->p;
-    tmp.tab_dev = (int *)h.tab->p;
-  } else if (!tmp.ds.empty()) {
-    while (!g_bsgs.empty() && g_bsgs_bytes + tmp.bytes > diag_cache_cap()) {
-      pool_free(g_bsgs.back().pts);
-      pool_free(g_bsgs.back().tab_dev);
-      g_bsgs_bytes -= g_bsgs.back().bytes;
-      g_bsgs.pop_back();
-    }
-    tmp.pts = (uint64_t *)pool_alloc(tmp.bytes);
-    tmp.tab_dev = (int *)pool_alloc(tabw * 8);
-  }
-  if (!tmp.ds.empty()) {
-    bsgs_encode(tmp, Md, lvl, g, tmp.pts);
-    upload(tmp.tab_dev, tmp.tab.data(), tmp.tab.size() * sizeof(int));
-  }
-  if (h.pts || tmp.ds.empty())
-    return &tmp;
-  tmp.M.assign(Md, Md + mwords);  // the owned copy: made on a miss only
-  tmp.s = s;
-  tmp.lvl = lvl;
-  tmp.g = g;
-  g_bsgs_bytes += tmp.bytes;
-  g_bsgs.push_front(std::move(tmp));
-  return &g_bsgs.front();
+  return g_bsgs.get(
+    h, {s, lvl, g}, lvl, Md, nullptr, 2 * (size_t)s * s, [&](BsgsPlan &p) { bsgs_plan(p.a, Md, g); },
+    [&](const BsgsPlan &p, uint64_t *pts) { bsgs_encode(p.a, Md, lvl, g, pts); });
 }
 
 // Every rotation a plan uses and its key (found before anything is launched).
 struct BsgsKeys {
-  unsigned nbs, nj;      // baby slots, giant steps
-  unsigned has0, nbr;    // slot 0 is x itself; rotated baby slots
-  unsigned hasj0, njr;   // giant step 0 is not rotated; rotated giant steps
+  unsigned nbs = 0, nj = 0;      // baby slots, giant steps
+  unsigned has0 = 0, nbr = 0;    // slot 0 is x itself; rotated baby slots
+  unsigned hasj0 = 0, njr = 0;   // giant step 0 is not rotated; rotated giant steps
   std::vector<unsigned> brot, grot;
   std::vector<const he_evk_t *> bkey, gkey;
   std::vector<uint64_t> bgal, ggal;
 };
 
-static BsgsKeys bsgs_find_keys(const BsgsPlan &plan, const he_evk_t rk[], unsigned g)
+// The keys of the baby rotations `baby` and of the giant steps `giant` (step j
+// is the rotation j g); either list may be empty.
+static BsgsKeys bsgs_find_keys(const std::vector<unsigned> &baby, const std::vector<unsigned> &giant, unsigned g,
+                               const he_evk_t rk[])
 {
   BsgsKeys k;
-  k.nbs = (unsigned)plan.baby.size();
-  k.nj = (unsigned)plan.giant.size();
-  k.has0 = k.nbs && plan.baby[0] == 0;
+  k.nbs = (unsigned)baby.size();
+  k.nj = (unsigned)giant.size();
+  k.has0 = k.nbs && baby[0] == 0;
   k.nbr = k.nbs - k.has0;
-  k.hasj0 = k.nj && plan.giant[0] == 0;
+  k.hasj0 = k.nj && giant[0] == 0;
   k.njr = k.nj - k.hasj0;
   k.brot.resize(k.nbr);
   k.bkey.resize(k.nbr);
@@ -3109,12 +3165,12 @@ static BsgsKeys bsgs_find_keys(const BsgsPlan &plan, const he_evk_t rk[], unsign
   k.gkey.resize(k.njr);
   k.ggal.resize(k.njr);
   for (unsigned r = 0; r < k.nbr; r++) {
-    k.brot[r] = plan.baby[k.has0 + r];
+    k.brot[r] = baby[k.has0 + r];
     k.bgal[r] = galois_of_rot(k.brot[r]);
     k.bkey[r] = find_rot_key(rk, k.brot[r], k.bgal[r]);
   }
   for (unsigned r = 0; r < k.njr; r++) {
-    k.grot[r] = plan.giant[k.hasj0 + r] * g;
+    k.grot[r] = giant[k.hasj0 + r] * g;
     k.ggal[r] = galois_of_rot(k.grot[r]);
     k.gkey[r] = find_rot_key(rk, k.grot[r], k.ggal[r]);
   }
@@ -3212,16 +3268,16 @@ extern "C" void he_gemv_bsgs(he_ct_t *y, const gpqhe_complex_t M[], const he_ct_
   const size_t n = G.n, pw = (size_t)lvl * n;
   const size_t budget = bsgs_budget();
 
-  BsgsPlanHold hold;
+  PlanHold hold;
   const BsgsPlan *plan = bsgs_plan_get(hold, (const double *)M, lvl, g);
   prov_forget(y->data, pstride(y));
-  if (plan->ds.empty()) {  // all-zero matrix
+  if (plan->a.ds.empty()) {  // all-zero matrix
     for (unsigned p = 0; p < 2; p++)
       HIP_CHECK(hipMemsetAsync(limb(y, p, 0), 0, (size_t)(lvl - 1) * n * 8, G.stream));
     gemv_set_meta(y, x, lvl);
     return;
   }
-  const BsgsKeys k = bsgs_find_keys(*plan, rk, g);
+  const BsgsKeys k = bsgs_find_keys(plan->a.baby, plan->a.giant, g, rk);
 
   // baby steps: B [nbs][2][lvl][n]
   Ws B((size_t)k.nbs * 2 * pw);
@@ -3229,7 +3285,7 @@ extern "C" void he_gemv_bsgs(he_ct_t *y, const gpqhe_complex_t M[], const he_ct_
 
   // the plaintext inner sums: U [nj][2][lvl][n]
   Ws U((size_t)k.nj * 2 * pw);
-  k_bsgs_inner(U.p, B.p, plan->pts, plan->tab_dev, k.nj, k.nbs, (unsigned)plan->ds.size(), lvl);
+  k_bsgs_inner(U.p, B.p, plan->pts, plan->tab_dev, k.nj, k.nbs, (unsigned)plan->a.ds.size(), lvl);
 
   // giant steps: each u_j (j >= 1) rotated by j g through its own ModDown,
   // then summed (with u_0) over the q limbs; chunks of cg giant steps
@@ -3614,245 +3670,48 @@ extern "C" void he_rot_batch(uint64_t *out, const uint64_t *x, size_t count, uns
 }
 
 // ---------------------------------------------------------------------------
-// he_gemv_bsgs_batch (include/gpqhe_ext_batch.h): he_gemv_bsgs over count
-// ciphertexts that share M, g and the keys.  One plan lookup per call; the
-// ciphertexts in chunks that fit GPQHE_WS_MIB; inside a chunk the buffers are
-// slot-major -- B [baby slot][ct][2][lvl][n], U and R [giant step][ct][2][lvl][n]
-// -- so a rotation of the whole chunk is one contiguous batch for the windowed
-// path (k_gemv_batch with the rotation's fold, as he_rot_batch), and the inner
+// The batch products over BSGS plans: he_gemv_bsgs_batch here, the pair, the
+// step and the row-folded and packed forms below.  One plan lookup per call;
+// the ciphertexts in chunks that fit GPQHE_WS_MIB; inside a chunk the buffers
+// are slot-major -- B [baby slot][ct][2][lvl][n], U [giant step][ct][2][lvl][n]
+// and the rotated giant steps R likewise -- so a rotation of the whole chunk is
+// one contiguous batch for the windowed path (win_rot_chunk), and the inner
 // sums share every encoded diagonal word among a tile of ciphertexts
 // (bsgs_inner_batch_kernel).  Where the windowed path is off, the single
 // call's hoisted stages run per ciphertext into the same buffers.  Every step
 // gives the residues of he_gemv_bsgs's.
 // ---------------------------------------------------------------------------
-static void bsgs_batch_chunk(uint64_t *y, const uint64_t *x, unsigned cnt, unsigned lvl, const BsgsPlan &plan,
-                             const BsgsKeys &k, const he_evk_t rk[], size_t budget)
-{
-  const unsigned nm = lvl + G.K, ndig = (lvl + G.alpha - 1) / G.alpha;
-  const size_t n = G.n, pw = (size_t)lvl * n, cw = 2 * pw, sw = (size_t)cnt * cw;  // words: ciphertext, slot
-  const bool win = gemv_win_on(lvl);
-  Ws B((size_t)k.nbs * sw), U((size_t)k.nj * sw), R((size_t)k.njr * sw);
-
-  // baby steps
-  if (win) {
-    if (k.has0)
-      HIP_CHECK(hipMemcpyAsync(B.p, x, sw * 8, hipMemcpyDeviceToDevice, G.stream));
-    for (unsigned r = 0; r < k.nbr; r++) {
-      const RotFold &f = bsgs_rot_fold(k.brot[r], lvl, rk);
-      RotFoldUse use(f);
-      k_gemv_batch(B.p + (size_t)(k.has0 + r) * sw, x, cnt, lvl, f.K, &f.rot, 1, 0);
-    }
-  } else {
-    for (unsigned c = 0; c < cnt; c++) {
-      const he_ct_t cx = ct_view(x + c * cw, lvl);
-      bsgs_baby(B.p + c * cw, sw, &cx, k, lvl, budget);
-    }
-  }
-
-  // the inner sums of every ciphertext
-  k_bsgs_inner_batch(U.p, B.p, plan.pts, plan.tab_dev, k.nj, k.nbs, (unsigned)plan.ds.size(), lvl, cnt);
-
-  // giant steps: u_j of the whole chunk rotated by j g into R
-  if (win) {
-    for (unsigned r = 0; r < k.njr; r++) {
-      const RotFold &f = bsgs_rot_fold(k.grot[r], lvl, rk);
-      RotFoldUse use(f);
-      k_gemv_batch(R.p + (size_t)r * sw, U.p + (size_t)(k.hasj0 + r) * sw, cnt, lvl, f.K, &f.rot, 1, 0);
-    }
-  } else if (k.njr) {
-    const unsigned cg = bsgs_giant_chunk(k, lvl, budget, 0);
-    Ws Dg((size_t)cg * ndig * nm * n), acc((size_t)cg * 2 * nm * n);
-    for (unsigned c = 0; c < cnt; c++)
-      for (unsigned r0 = 0; r0 < k.njr; r0 += cg)
-        bsgs_giant(R.p + (size_t)r0 * sw + c * cw, sw, U.p + c * cw, sw, k, r0, std::min(cg, k.njr - r0), lvl, Dg.p,
-                   acc.p);
-  }
-
-  // sum over the giant steps (u_0 is not rotated) and rescale by q_top into y
-  uint64_t *S = U.p;
-  Ws Sw(k.njr ? sw : 0);
-  if (k.njr) {
-    k_bsgs_sum_batch(Sw.p, k.hasj0 ? U.p : nullptr, R.p, k.njr, sw, lvl, cnt);
-    S = Sw.p;
-  }
-  k_moddown(y, (size_t)(lvl - 1) * n, S, pw, 2 * cnt, lvl, 2);
-}
-
-extern "C" void he_gemv_bsgs_batch(uint64_t *y, const gpqhe_complex_t M[], const uint64_t *x, size_t count,
-                                   unsigned int nlimbs, const he_evk_t rk[], unsigned int g)
-{
-  HPROF("gemv_bsgs_batch");
-  check_ctx();
-  const unsigned s = G.slots, lvl = nlimbs;
-  if (lvl < 2 || lvl > G.L)
-    gpqhe_die("he_gemv_bsgs_batch: bad level %u", lvl);
-  if (!g)
-    g = bsgs_default_g();
-  if (g > s)
-    gpqhe_die("he_gemv_bsgs_batch: g = %u > slots = %u", g, s);
-  const unsigned nm = lvl + G.K, ndig = (lvl + G.alpha - 1) / G.alpha;
-  const size_t n = G.n, pw = (size_t)lvl * n, in_words = 2 * pw, out_words = 2 * (size_t)(lvl - 1) * n;
-  if (!count)
-    return;
-  if (y < x + count * in_words && x < y + count * out_words)
-    gpqhe_die("he_gemv_bsgs_batch: output overlaps the input");
-
-  BsgsPlanHold hold;
-  const BsgsPlan *plan = bsgs_plan_get(hold, (const double *)M, lvl, g);
-  if (plan->ds.empty()) {  // all-zero matrix
-    HIP_CHECK(hipMemsetAsync(y, 0, count * out_words * 8, G.stream));
-    return;
-  }
-  const BsgsKeys k = bsgs_find_keys(*plan, rk, g);
-
-  // a ciphertext's share of a chunk: its baby slots, giant steps, rotated
-  // giants and sum, and on the windowed path k_gemv_batch's workspace (the
-  // generic stages' workspaces do not grow with the chunk)
-  const size_t budget = bsgs_budget();
-  const size_t per_ct = (size_t)(k.nbs + k.nj + k.njr + 1) * 2 * pw +
-                        (gemv_win_on(lvl) ? ((size_t)lvl + (size_t)ndig * nm + 2 * (size_t)nm) * n : 0);
-  size_t chunk = std::min<size_t>(std::max<size_t>(1, budget / per_ct), 16384);
-  if (const char *e = getenv("GPQHE_BSGS_CHUNK"))  // test hook: several chunks on a small batch
-    chunk = std::max<size_t>(1, std::min<size_t>(chunk, strtoul(e, nullptr, 0)));
-  else  // equal chunks: a short last one runs at a fraction of the GPU's width
-    chunk = (count + (count + chunk - 1) / chunk - 1) / ((count + chunk - 1) / chunk);
-  for (size_t c0 = 0; c0 < count; c0 += chunk) {
-    const unsigned cnt = (unsigned)std::min(chunk, count - c0);
-    bsgs_batch_chunk(y + c0 * out_words, x + c0 * in_words, cnt, lvl, *plan, k, rk, budget);
-  }
-}
-
-// ---------------------------------------------------------------------------
-// he_gemv2_bsgs_batch / he_hempc_step_batch (include/gpqhe_ext_step_batch.h):
-// y = Ma xa + Mb xb by one BSGS over both operands, and ctr_hempc around it.
-// The two products are summed before the giant rotations, so the inner sums
-// run over the concatenated baby slots of both operands and every giant step
-// of the union is rotated once: 2 (g - 1) + (G - 1) key switches and one
-// rescale per ciphertext.  The stages are he_gemv_bsgs_batch's (same kernels,
-// same slot-major buffers); the step adds step_diff_batch_kernel in front and
-// step_tail_batch_kernel behind (step_batch.hip).
-//
-// The pair plan: one cache entry per (Ma, Mb, level, g), the ordered pair, in
-// a list of its own with bsgs_plan_get's rules -- one lookup per call before
-// the first launch, every eviction there, the entry owns its blocks, bounded by
-// diag_cache_cap(), a larger plan lives in the call's holder, hectx_exit
-// empties it.  It shares nothing with g_bsgs: what he_gemv_bsgs and
-// he_gemv_bsgs_batch look up does not change.
-// ---------------------------------------------------------------------------
-struct Bsgs2Plan {
-  std::vector<double> Ma, Mb;   // the matrices it was made from (compared in place on a lookup)
-  unsigned s = 0, lvl = 0, g = 0;
-  BsgsPlan a, b;                // each operand's diagonals, baby list and giant steps (host lists only)
-  std::vector<unsigned> giant;  // the union of their giant steps, ascending: row order of tab and U
-  std::vector<int> tab;         // [giant][baby slots of a | baby slots of b] -> index into pts, -1: none
-  uint64_t *pts = nullptr;      // [a.ds.size() + b.ds.size()][lvl][n]: a's diagonals, then b's
-  int *tab_dev = nullptr;
-  size_t bytes = 0;
-};
-static std::list<Bsgs2Plan> g_bsgs2;
-static size_t g_bsgs2_bytes = 0;
-
-static void bsgs2_cache_clear()
-{
-  for (Bsgs2Plan &p : g_bsgs2) {
-    pool_free(p.pts);
-    pool_free(p.tab_dev);
-  }
-  g_bsgs2.clear();
-  g_bsgs2_bytes = 0;
-}
-
-struct Bsgs2PlanHold {
-  Bsgs2Plan tmp;
-  std::unique_ptr<Ws> pts, tab;
-};
-
-static const Bsgs2Plan *bsgs2_plan_get(Bsgs2PlanHold &h, const double *Ma, const double *Mb, unsigned lvl, unsigned g)
-{
-  const unsigned s = G.slots;
-  const size_t pw = (size_t)lvl * G.n, mwords = 2 * (size_t)s * s;
-  for (auto it = g_bsgs2.begin(); it != g_bsgs2.end(); ++it)
-    if (it->s == s && it->lvl == lvl && it->g == g && !memcmp(it->Ma.data(), Ma, mwords * 8) &&
-        !memcmp(it->Mb.data(), Mb, mwords * 8)) {
-      g_bsgs2.splice(g_bsgs2.begin(), g_bsgs2, it);
-      return &g_bsgs2.front();
-    }
-  Bsgs2Plan &tmp = h.tmp;
-  bsgs_plan(tmp.a, Ma, g);
-  bsgs_plan(tmp.b, Mb, g);
-  const size_t nda = tmp.a.ds.size(), ndiag = nda + tmp.b.ds.size();
-  if (!ndiag)
-    return &tmp;  // both matrices zero: no blocks
-  std::set_union(tmp.a.giant.begin(), tmp.a.giant.end(), tmp.b.giant.begin(), tmp.b.giant.end(),
-                 std::back_inserter(tmp.giant));
-  const size_t na = tmp.a.baby.size(), nb = tmp.b.baby.size(), gs = na + nb;
-  tmp.tab.assign(tmp.giant.size() * gs, -1);
-  for (size_t r = 0, ja = 0, jb = 0; r < tmp.giant.size(); r++) {
-    if (ja < tmp.a.giant.size() && tmp.a.giant[ja] == tmp.giant[r]) {
-      for (size_t i = 0; i < na; i++)
-        tmp.tab[r * gs + i] = tmp.a.tab[ja * na + i];
-      ja++;
-    }
-    if (jb < tmp.b.giant.size() && tmp.b.giant[jb] == tmp.giant[r]) {
-      for (size_t i = 0; i < nb; i++)
-        if (tmp.b.tab[jb * nb + i] >= 0)
-          tmp.tab[r * gs + na + i] = (int)nda + tmp.b.tab[jb * nb + i];
-      jb++;
-    }
-  }
-  const size_t tabw = (tmp.tab.size() * sizeof(int) + 7) / 8;
-  tmp.bytes = ndiag * pw * 8;
-  if (tmp.bytes > diag_cache_cap()) {
-    h.pts.reset(new Ws(ndiag * pw));
-    h.tab.reset(new Ws(tabw));
-    tmp.pts = h.pts->p;
-    tmp.tab_dev = (int *)h.tab->p;
-  } else {
-    while (!g_bsgs2.empty() && g_bsgs2_bytes + tmp.bytes > diag_cache_cap()) {
-      pool_free(g_bsgs2.back().pts);
-      pool_free(g_bsgs2.back().tab_dev);
-      g_bsgs2_bytes -= g_bsgs2.back().bytes;
-      g_bsgs2.pop_back();
-    }
-    tmp.pts = (uint64_t *)pool_alloc(tmp.bytes);
-    tmp.tab_dev = (int *)pool_alloc(tabw * 8);
-  }
-  bsgs_encode(tmp.a, Ma, lvl, g, tmp.pts);
-  bsgs_encode(tmp.b, Mb, lvl, g, tmp.pts + nda * pw);
-  upload(tmp.tab_dev, tmp.tab.data(), tmp.tab.size() * sizeof(int));
-  if (h.pts)
-    return &tmp;
-  tmp.Ma.assign(Ma, Ma + mwords);  // the owned copies: made on a miss only
-  tmp.Mb.assign(Mb, Mb + mwords);
-  tmp.s = s;
-  tmp.lvl = lvl;
-  tmp.g = g;
-  g_bsgs2_bytes += tmp.bytes;
-  g_bsgs2.push_front(std::move(tmp));
-  return &g_bsgs2.front();
-}
-
-// The four inputs of a step (null: he_gemv2_bsgs_batch, whose operands are given).
+// The four inputs of a step (null: the operands are given).
 struct StepIn {
   const uint64_t *xhat, *xr, *uhat, *ur;
 };
 
-// Baby stage of one operand over a chunk, as bsgs_batch_chunk's: slot i of B
-// ([k.nbs][cnt][2][lvl][n]) <- rot(x, baby[i]); x may already be slot 0.
-static void bsgs2_baby(uint64_t *B, const uint64_t *x, unsigned cnt, unsigned lvl, const BsgsKeys &k,
-                       const he_evk_t rk[], size_t budget, bool win)
+// The windowed rotation of whole slot-major chunks: out + t sw <- rot(x + t
+// x_stride, rot[t]) for t < nrot, each one k_gemv_batch with the rotation's
+// fold (as he_rot_batch).
+static void win_rot_chunk(uint64_t *out, const uint64_t *x, size_t x_stride, const unsigned *rot, unsigned nrot,
+                          unsigned cnt, unsigned lvl, const he_evk_t rk[])
+{
+  const size_t sw = (size_t)cnt * 2 * lvl * G.n;
+  for (unsigned t = 0; t < nrot; t++) {
+    const RotFold &f = bsgs_rot_fold(rot[t], lvl, rk);
+    RotFoldUse use(f);
+    k_gemv_batch(out + t * sw, x + t * x_stride, cnt, lvl, f.K, &f.rot, 1, 0);
+  }
+}
+
+// Baby stage of one operand over a chunk: slot i of B ([k.nbs][cnt][2][lvl][n])
+// <- rot(x, baby[i]); x may already be slot 0.
+static void bsgs_baby_chunk(uint64_t *B, const uint64_t *x, unsigned cnt, unsigned lvl, const BsgsKeys &k,
+                            const he_evk_t rk[], size_t budget)
 {
   const size_t cw = 2 * (size_t)lvl * G.n, sw = (size_t)cnt * cw;
   if (!k.nbs)
     return;
-  if (win) {
+  if (gemv_win_on(lvl)) {
     if (k.has0 && B != x)
       HIP_CHECK(hipMemcpyAsync(B, x, sw * 8, hipMemcpyDeviceToDevice, G.stream));
-    for (unsigned r = 0; r < k.nbr; r++) {
-      const RotFold &f = bsgs_rot_fold(k.brot[r], lvl, rk);
-      RotFoldUse use(f);
-      k_gemv_batch(B + (size_t)(k.has0 + r) * sw, x, cnt, lvl, f.K, &f.rot, 1, 0);
-    }
+    win_rot_chunk(B + (size_t)k.has0 * sw, x, 0, k.brot.data(), k.nbr, cnt, lvl, rk);
     return;
   }
   for (unsigned c = 0; c < cnt; c++) {
@@ -3861,19 +3720,23 @@ static void bsgs2_baby(uint64_t *B, const uint64_t *x, unsigned cnt, unsigned lv
   }
 }
 
-// One chunk of cnt ciphertexts: ka / kb the baby rotations of each operand, kg
-// the giant steps of the union.  st: form xa = xhat - xr and xb = uhat - ur
-// first (into slot 0 of the operand's baby slots where its plan uses the
-// unrotated slot, else into a workspace) and finish with y = uhat - y.
-static void bsgs2_chunk(uint64_t *y, const uint64_t *xa, const uint64_t *xb, const StepIn *st, unsigned cnt,
-                        unsigned lvl, const Bsgs2Plan &plan, const BsgsKeys &ka, const BsgsKeys &kb,
-                        const BsgsKeys &kg, const he_evk_t rk[], size_t budget)
+// One chunk of cnt ciphertexts, y = Ma xa + Mb xb: ka / kb the baby rotations
+// of each operand (kb empty: the single product), kg the giant steps of the
+// union, fold the rotate-and-add steps at level lvl - 1 behind the rescale.
+// st: form xa = xhat - xr and xb = uhat - ur first (into slot 0 of the
+// operand's baby slots where its plan uses the unrotated slot, else into a
+// workspace) and finish with y = uhat - y: the last fold step's kernel, or
+// k_step_tail_batch where there is no fold.
+static void bsgs_chunk(uint64_t *y, const uint64_t *xa, const uint64_t *xb, const StepIn *st, unsigned cnt,
+                       unsigned lvl, const BsgsPlan &plan, const BsgsKeys &ka, const BsgsKeys &kb, const BsgsKeys &kg,
+                       const std::vector<unsigned> &fold, const he_evk_t rk[], size_t budget)
 {
   const unsigned nm = lvl + G.K, ndig = (lvl + G.alpha - 1) / G.alpha;
   const size_t n = G.n, pw = (size_t)lvl * n, cw = 2 * pw, sw = (size_t)cnt * cw;  // words: ciphertext, slot
-  const bool win = gemv_win_on(lvl);
+  const size_t ow = 2 * (size_t)(lvl - 1) * n;                                     // ... of y
   const unsigned nbs = ka.nbs + kb.nbs;
-  // (the rotated giant steps take the baby slots' place: the inner sums are the last to read those)
+  // (the rotated giant steps, then the fold's rotated copy, take the baby
+  // slots' place: the inner sums are the last to read those)
   Ws B((size_t)std::max(nbs, kg.njr) * sw), U((size_t)kg.nj * sw);
   uint64_t *Ba = B.p, *Bb = B.p + (size_t)ka.nbs * sw, *R = B.p;
 
@@ -3885,19 +3748,14 @@ static void bsgs2_chunk(uint64_t *y, const uint64_t *xa, const uint64_t *xb, con
     xb = ud;
   }
 
-  // baby steps of both operands, then the inner sums over all of their slots
-  bsgs2_baby(Ba, xa, cnt, lvl, ka, rk, budget, win);
-  bsgs2_baby(Bb, xb, cnt, lvl, kb, rk, budget, win);
-  k_bsgs_inner_batch(U.p, B.p, plan.pts, plan.tab_dev, kg.nj, nbs, (unsigned)(plan.a.ds.size() + plan.b.ds.size()), lvl,
-                     cnt);
+  // baby steps of each operand, then the inner sums over all of their slots
+  bsgs_baby_chunk(Ba, xa, cnt, lvl, ka, rk, budget);
+  bsgs_baby_chunk(Bb, xb, cnt, lvl, kb, rk, budget);
+  k_bsgs_inner_batch(U.p, B.p, plan.pts, plan.tab_dev, kg.nj, nbs, plan.ndiag(), lvl, cnt);
 
   // giant steps of the union: u_j of the whole chunk rotated by j g into R
-  if (win) {
-    for (unsigned r = 0; r < kg.njr; r++) {
-      const RotFold &f = bsgs_rot_fold(kg.grot[r], lvl, rk);
-      RotFoldUse use(f);
-      k_gemv_batch(R + (size_t)r * sw, U.p + (size_t)(kg.hasj0 + r) * sw, cnt, lvl, f.K, &f.rot, 1, 0);
-    }
+  if (gemv_win_on(lvl)) {
+    win_rot_chunk(R, U.p + (size_t)kg.hasj0 * sw, sw, kg.grot.data(), kg.njr, cnt, lvl, rk);
   } else if (kg.njr) {
     const unsigned cg = bsgs_giant_chunk(kg, lvl, budget, 0);
     Ws Dg((size_t)cg * ndig * nm * n), acc((size_t)cg * 2 * nm * n);
@@ -3907,7 +3765,7 @@ static void bsgs2_chunk(uint64_t *y, const uint64_t *xa, const uint64_t *xb, con
                    acc.p);
   }
 
-  // sum over the giant steps, rescale by q_top into y, and the step's tail
+  // sum over the giant steps (u_0 is not rotated) and rescale by q_top into y
   uint64_t *S = U.p;
   Ws Sw(kg.njr ? sw : 0);
   if (kg.njr) {
@@ -3915,22 +3773,44 @@ static void bsgs2_chunk(uint64_t *y, const uint64_t *xa, const uint64_t *xb, con
     S = Sw.p;
   }
   k_moddown(y, (size_t)(lvl - 1) * n, S, pw, 2 * cnt, lvl, 2);
-  if (st)
+
+  // the fold at level lvl - 1: the whole chunk rotated into R, then accumulated
+  for (size_t t = 0; t < fold.size(); t++) {
+    if (gemv_win_on(lvl - 1)) {
+      win_rot_chunk(R, y, 0, &fold[t], 1, cnt, lvl - 1, rk);
+    } else {
+      for (unsigned c = 0; c < cnt; c++) {
+        he_ct_t cx = ct_view(y + c * ow, lvl - 1), co = ct_view(R + c * ow, lvl - 1);
+        he_rot(&co, &cx, fold[t], rk);
+      }
+    }
+    if (st && t + 1 == fold.size())
+      k_rows_fold_tail_batch(y, R, st->uhat, lvl, cnt);
+    else
+      k_rows_fold_add_batch(y, R, lvl - 1, cnt);
+  }
+  if (st && fold.empty())
     k_step_tail_batch(y, st->uhat, lvl, cnt);
 }
 
-static void bsgs2_run(const char *who, uint64_t *y, const double *Ma, const double *Mb, const uint64_t *xa,
-                      const uint64_t *xb, const StepIn *st, size_t count, unsigned lvl, const he_evk_t rk[],
-                      unsigned g)
+// What an entry point's own argument checks leave for the run: the rotation
+// of giant step 1 and the fold steps.
+struct BatchKind {
+  unsigned g;
+  std::vector<unsigned> fold;
+};
+
+// The run of every entry point: check() makes the entry point's own argument
+// checks (after the level's), get(hold) looks its plan up.  Plan, then keys,
+// then the first launch.
+template <class Check, class Get>
+static void bsgs_run(const char *who, uint64_t *y, const uint64_t *xa, const uint64_t *xb, const StepIn *st,
+                     size_t count, unsigned lvl, const he_evk_t rk[], Check check, Get get)
 {
   check_ctx();
-  const unsigned s = G.slots;
   if (lvl < 2 || lvl > G.L)
     gpqhe_die("%s: bad level %u", who, lvl);
-  if (!g)
-    g = bsgs_default_g();
-  if (g > s)
-    gpqhe_die("%s: g = %u > slots = %u", who, g, s);
+  const BatchKind kind = check();
   const unsigned nm = lvl + G.K, ndig = (lvl + G.alpha - 1) / G.alpha;
   const size_t n = G.n, pw = (size_t)lvl * n, in_words = 2 * pw, out_words = 2 * (size_t)(lvl - 1) * n;
   if (!count)
@@ -3938,11 +3818,11 @@ static void bsgs2_run(const char *who, uint64_t *y, const double *Ma, const doub
   const uint64_t *ins[4] = {st ? st->xhat : xa, st ? st->xr : xb, st ? st->uhat : nullptr, st ? st->ur : nullptr};
   for (const uint64_t *x : ins)
     if (x && y < x + count * in_words && x < y + count * out_words)
-      gpqhe_die("%s: output overlaps an input", who);
+      gpqhe_die("%s: output overlaps %s input", who, ins[1] ? "an" : "the");
 
-  Bsgs2PlanHold hold;
-  const Bsgs2Plan *plan = bsgs2_plan_get(hold, Ma, Mb, lvl, g);
-  if (plan->giant.empty()) {  // both matrices zero: y = 0, up = the lower limbs of uhat
+  PlanHold hold;
+  const BsgsPlan *plan = get(hold);
+  if (plan->giant.empty()) {  // no diagonal: y = 0, up = the lower limbs of uhat
     HIP_CHECK(hipMemsetAsync(y, 0, count * out_words * 8, G.stream));
     for (size_t c0 = 0; st && c0 < count; c0 += 16384) {
       const unsigned cnt = (unsigned)std::min<size_t>(16384, count - c0);
@@ -3950,37 +3830,94 @@ static void bsgs2_run(const char *who, uint64_t *y, const double *Ma, const doub
     }
     return;
   }
-  BsgsPlan t;  // every key is found before anything is launched
-  t.baby = plan->a.baby;
-  const BsgsKeys ka = bsgs_find_keys(t, rk, g);
-  t.baby = plan->b.baby;
-  const BsgsKeys kb = bsgs_find_keys(t, rk, g);
-  t.baby.clear();
-  t.giant = plan->giant;
-  const BsgsKeys kg = bsgs_find_keys(t, rk, g);
+  // every key is found before anything is launched
+  const BsgsKeys ka = bsgs_find_keys(plan->a.baby, {}, kind.g, rk), kb = bsgs_find_keys(plan->b.baby, {}, kind.g, rk);
+  const BsgsKeys kg = bsgs_find_keys({}, plan->giant, kind.g, rk);
+  for (unsigned r : kind.fold)
+    find_rot_key(rk, r, galois_of_rot(r));
 
   // a ciphertext's share of a chunk, in words of one ciphertext (2 lvl n):
-  //   max(nbs_a + nbs_b, njr)  the baby slots of both operands, later the rotated giant steps
-  //   + nj + 1                 the giant steps of the union and the sum
+  //   max(nbs_a + nbs_b, njr)  the baby slots of the operands, later the rotated giant steps
+  //                            (and the fold's rotated copy, which is smaller)
+  //   + nj                     the giant steps of the union
+  //   + 1                      their sum, where a giant step is rotated
   //   + 1 per operand of a step whose difference has no slot 0 to live in;
   // on the windowed path k_gemv_batch's workspace besides (the generic stages'
   // workspaces do not grow with the chunk)
   const size_t budget = bsgs_budget();
-  const size_t slots_ct = std::max(ka.nbs + kb.nbs, kg.njr) + kg.nj + 1 + (st ? !ka.has0 + !kb.has0 : 0);
+  const size_t slots_ct =
+    std::max(ka.nbs + kb.nbs, kg.njr) + kg.nj + (kg.njr ? 1 : 0) + (st ? !ka.has0 + !kb.has0 : 0);
   const size_t per_ct =
     slots_ct * 2 * pw + (gemv_win_on(lvl) ? ((size_t)lvl + (size_t)ndig * nm + 2 * (size_t)nm) * n : 0);
   size_t chunk = std::min<size_t>(std::max<size_t>(1, budget / per_ct), 16384);
   if (const char *e = getenv("GPQHE_BSGS_CHUNK"))  // test hook: several chunks on a small batch
     chunk = std::max<size_t>(1, std::min<size_t>(chunk, strtoul(e, nullptr, 0)));
-  else  // equal chunks, as he_gemv_bsgs_batch
+  else  // equal chunks: a short last one runs at a fraction of the GPU's width
     chunk = (count + (count + chunk - 1) / chunk - 1) / ((count + chunk - 1) / chunk);
   for (size_t c0 = 0; c0 < count; c0 += chunk) {
     const unsigned cnt = (unsigned)std::min(chunk, count - c0);
     const size_t o = c0 * in_words;
     const StepIn sc = st ? StepIn{st->xhat + o, st->xr + o, st->uhat + o, st->ur + o} : StepIn{};
-    bsgs2_chunk(y + c0 * out_words, st ? nullptr : xa + o, st ? nullptr : xb + o, st ? &sc : nullptr, cnt, lvl, *plan,
-                ka, kb, kg, rk, budget);
+    bsgs_chunk(y + c0 * out_words, st ? nullptr : xa + o, st || !xb ? nullptr : xb + o, st ? &sc : nullptr, cnt, lvl,
+               *plan, ka, kb, kg, kind.fold, rk, budget);
   }
+}
+
+// g = 0: the default; g > slots: an error (the check() of the forms with giant steps)
+static BatchKind bsgs_check_g(const char *who, unsigned &g)
+{
+  if (!g)
+    g = bsgs_default_g();
+  if (g > G.slots)
+    gpqhe_die("%s: g = %u > slots = %u", who, g, G.slots);
+  return BatchKind{g, {}};
+}
+
+// he_gemv_bsgs_batch (include/gpqhe_ext_batch.h): he_gemv_bsgs over count
+// ciphertexts that share M, g and the keys.
+extern "C" void he_gemv_bsgs_batch(uint64_t *y, const gpqhe_complex_t M[], const uint64_t *x, size_t count,
+                                   unsigned int nlimbs, const he_evk_t rk[], unsigned int g)
+{
+  HPROF("gemv_bsgs_batch");
+  bsgs_run(
+    "he_gemv_bsgs_batch", y, x, nullptr, nullptr, count, nlimbs, rk,
+    [&] { return bsgs_check_g("he_gemv_bsgs_batch", g); },
+    [&](PlanHold &h) { return bsgs_plan_get(h, (const double *)M, nlimbs, g); });
+}
+
+// ---------------------------------------------------------------------------
+// he_gemv2_bsgs_batch / he_hempc_step_batch (include/gpqhe_ext_step_batch.h):
+// y = Ma xa + Mb xb by one BSGS over both operands, and ctr_hempc around it.
+// The two products are summed before the giant rotations, so the inner sums
+// run over the concatenated baby slots of both operands and every giant step
+// of the union is rotated once: 2 (g - 1) + (G - 1) key switches and one
+// rescale per ciphertext.  The step adds step_diff_batch_kernel in front and
+// step_tail_batch_kernel behind (step_batch.hip).
+// ---------------------------------------------------------------------------
+// The pair plan: (Ma, Mb, lvl, g), the ordered pair, in g_bsgs2.
+static const BsgsPlan *bsgs2_plan_get(PlanHold &h, const double *Ma, const double *Mb, unsigned lvl, unsigned g)
+{
+  const unsigned s = G.slots;
+  const size_t pw = (size_t)lvl * G.n;
+  return g_bsgs2.get(
+    h, {s, lvl, g}, lvl, Ma, Mb, 2 * (size_t)s * s,
+    [&](BsgsPlan &p) {
+      bsgs_plan(p.a, Ma, g);
+      bsgs_plan(p.b, Mb, g);
+    },
+    [&](const BsgsPlan &p, uint64_t *pts) {
+      bsgs_encode(p.a, Ma, lvl, g, pts);
+      bsgs_encode(p.b, Mb, lvl, g, pts + p.a.ds.size() * pw);
+    });
+}
+
+static void bsgs2_run(const char *who, uint64_t *y, const double *Ma, const double *Mb, const uint64_t *xa,
+                      const uint64_t *xb, const StepIn *st, size_t count, unsigned lvl, const he_evk_t rk[],
+                      unsigned g)
+{
+  bsgs_run(
+    who, y, xa, xb, st, count, lvl, rk, [&] { return bsgs_check_g(who, g); },
+    [&](PlanHold &h) { return bsgs2_plan_get(h, Ma, Mb, lvl, g); });
 }
 
 extern "C" void he_gemv2_bsgs_batch(uint64_t *y, const gpqhe_complex_t Ma[], const uint64_t *xa,
@@ -4008,51 +3945,18 @@ extern "C" void he_hempc_step_batch(uint64_t *up, const gpqhe_complex_t Ma[], co
 // extended diagonals E_i (row k mod m' of the matrix at column k + i, zero
 // where k mod m' >= rows); their products with rot(x, i) are summed, rescaled,
 // and log2(s / m') rotate-and-add steps at level lvl - 1 gather the partial
-// sums: 2 (m' - 1) + log2(s / m') key switches per ciphertext.  The baby
-// rotations, the inner sums and the rescale are he_gemv2_bsgs_batch's stages
-// with one "giant step" (no giant rotation); the fold's additions are
-// rows_batch.hip's, the last one of a step fused with the step's tail.
-//
-// The row plan: one cache entry per (the leading rows s entries of Ma, of Mb,
-// level, rows), in a list of its own with bsgs2_plan_get's rules -- one lookup
-// per call before the first launch, every eviction there, the entry owns its
-// blocks, bounded by diag_cache_cap(), a larger plan lives in the call's
-// holder, hectx_exit empties it.
+// sums: 2 (m' - 1) + log2(s / m') key switches per ciphertext.  To bsgs_chunk
+// this is a pair plan with one giant step (no giant rotation) and a fold list;
+// the fold's additions are rows_batch.hip's, the last one of a step fused with
+// the step's tail.
 //
 // The packed forms (include/gpqhe_ext_packed_batch.h: he_gemv2_packed_batch,
 // he_hempc_step_packed_batch, he_genrk_packed) are the same code at a stride:
 // the context's S slots hold P = S / sl loops of sl slots, entry k of loop p
 // at slot k P + p, so E_i is filled over S slots from loop p's own matrix
 // (nmat = P) or the shared one (nmat = 1), baby rotation i is rotation i P and
-// fold step r is r P.  The entry points above are sl = S, nmat = 1 (P = 1);
-// the plan's key holds sl and nmat besides.
+// fold step r is r P.  The entry points above are sl = S, nmat = 1 (P = 1).
 // ---------------------------------------------------------------------------
-struct RowsPlan {
-  std::vector<double> Ma, Mb;  // the leading rows of the matrices it was made from ([nmat][rows][sl])
-  unsigned s = 0, lvl = 0, rows = 0, sl = 0, nmat = 0;
-  BsgsPlan a, b;               // .baby: the rotation i P of each operand's non-zero E_i, ascending (host lists only)
-  uint64_t *pts = nullptr;     // [a.baby.size() + b.baby.size()][lvl][n]: a's extended diagonals, then b's
-  int *tab_dev = nullptr;      // [1][baby slots of a | of b] -> index into pts (the identity)
-  size_t bytes = 0;
-};
-static std::list<RowsPlan> g_rows;
-static size_t g_rows_bytes = 0;
-
-static void rows_cache_clear()
-{
-  for (RowsPlan &p : g_rows) {
-    pool_free(p.pts);
-    pool_free(p.tab_dev);
-  }
-  g_rows.clear();
-  g_rows_bytes = 0;
-}
-
-struct RowsPlanHold {
-  RowsPlan tmp;
-  std::unique_ptr<Ws> pts, tab;
-};
-
 static unsigned rows_pow2(unsigned rows)
 {
   unsigned mp = 1;
@@ -4079,68 +3983,52 @@ static bool rows_diag(std::vector<double> &v, const double *Md, unsigned i, unsi
   return nz;
 }
 
-static const RowsPlan *rows_plan_get(RowsPlanHold &h, const double *Ma, const double *Mb, unsigned lvl, unsigned rows,
-                                     unsigned sl, unsigned nmat)
+// The non-zero E_i of M, i < m', as an operand with one giant step: ds the i,
+// baby the rotations i P, tab the identity.
+static void rows_plan(BsgsOp &o, const double *Md, unsigned rows, unsigned sl, unsigned nmat)
 {
-  const unsigned s = G.slots, P = s / sl, mp = rows_pow2(rows);
-  const size_t pw = (size_t)lvl * G.n, mwords = 2 * (size_t)nmat * rows * sl;
-  for (auto it = g_rows.begin(); it != g_rows.end(); ++it)
-    if (it->s == s && it->lvl == lvl && it->rows == rows && it->sl == sl && it->nmat == nmat &&
-        !memcmp(it->Ma.data(), Ma, mwords * 8) && !memcmp(it->Mb.data(), Mb, mwords * 8)) {
-      g_rows.splice(g_rows.begin(), g_rows, it);
-      return &g_rows.front();
+  const unsigned P = G.slots / sl, mp = rows_pow2(rows);
+  std::vector<double> v(2 * (size_t)G.slots);
+  for (unsigned i = 0; i < mp; i++)
+    if (rows_diag(v, Md, i, rows, mp, sl, nmat)) {
+      o.tab.push_back((int)o.ds.size());
+      o.ds.push_back(i);
+      o.baby.push_back(i * P);
     }
-  RowsPlan &tmp = h.tmp;
-  std::vector<double> v(2 * (size_t)s);
-  for (unsigned i = 0; i < mp; i++) {
-    if (rows_diag(v, Ma, i, rows, mp, sl, nmat))
-      tmp.a.baby.push_back(i * P);
-    if (rows_diag(v, Mb, i, rows, mp, sl, nmat))
-      tmp.b.baby.push_back(i * P);
-  }
-  const size_t na = tmp.a.baby.size(), ndiag = na + tmp.b.baby.size();
-  if (!ndiag)
-    return &tmp;  // both matrices zero in their leading rows: no blocks
-  std::vector<int> tab(ndiag);
-  for (size_t e = 0; e < ndiag; e++)
-    tab[e] = (int)e;
-  const size_t tabw = (ndiag * sizeof(int) + 7) / 8;
-  tmp.bytes = ndiag * pw * 8;
-  if (tmp.bytes > diag_cache_cap()) {
-    h.pts.reset(new Ws(ndiag * pw));
-    h.tab.reset(new Ws(tabw));
-    tmp.pts = h.pts->p;
-    tmp.tab_dev = (int *)h.tab->p;
-  } else {
-    while (!g_rows.empty() && g_rows_bytes + tmp.bytes > diag_cache_cap()) {
-      pool_free(g_rows.back().pts);
-      pool_free(g_rows.back().tab_dev);
-      g_rows_bytes -= g_rows.back().bytes;
-      g_rows.pop_back();
-    }
-    tmp.pts = (uint64_t *)pool_alloc(tmp.bytes);
-    tmp.tab_dev = (int *)pool_alloc(tabw * 8);
-  }
+  if (!o.ds.empty())
+    o.giant.push_back(0);
+}
+
+// pts <- E_i of every i in o.ds, in that order.
+static void rows_encode(const BsgsOp &o, const double *Md, unsigned lvl, unsigned rows, unsigned sl, unsigned nmat,
+                        uint64_t *pts)
+{
   unsigned mods[GPQHE_MAXMOD];
   for (unsigned l = 0; l < lvl; l++)
     mods[l] = l;
-  for (size_t e = 0; e < ndiag; e++) {
-    rows_diag(v, e < na ? Ma : Mb, (e < na ? tmp.a.baby[e] : tmp.b.baby[e - na]) / P, rows, mp, sl, nmat);
-    encode_limbs(tmp.pts + e * pw, v.data(), s, (double)G.q[lvl - 1], mods, lvl);
+  std::vector<double> v(2 * (size_t)G.slots);
+  for (size_t e = 0; e < o.ds.size(); e++) {
+    rows_diag(v, Md, o.ds[e], rows, rows_pow2(rows), sl, nmat);
+    encode_limbs(pts + e * ((size_t)lvl << G.logn), v.data(), G.slots, (double)G.q[lvl - 1], mods, lvl);
   }
-  upload(tmp.tab_dev, tab.data(), ndiag * sizeof(int));
-  if (h.pts)
-    return &tmp;
-  tmp.Ma.assign(Ma, Ma + mwords);  // the owned copies: made on a miss only
-  tmp.Mb.assign(Mb, Mb + mwords);
-  tmp.s = s;
-  tmp.lvl = lvl;
-  tmp.rows = rows;
-  tmp.sl = sl;
-  tmp.nmat = nmat;
-  g_rows_bytes += tmp.bytes;
-  g_rows.push_front(std::move(tmp));
-  return &g_rows.front();
+}
+
+// The row plan: (the leading rows sl entries of each of Ma's, of Mb's nmat
+// matrices, lvl, rows, sl, nmat) in g_rows.
+static const BsgsPlan *rows_plan_get(PlanHold &h, const double *Ma, const double *Mb, unsigned lvl, unsigned rows,
+                                     unsigned sl, unsigned nmat)
+{
+  const size_t pw = (size_t)lvl * G.n;
+  return g_rows.get(
+    h, {G.slots, lvl, rows, sl, nmat}, lvl, Ma, Mb, 2 * (size_t)nmat * rows * sl,
+    [&](BsgsPlan &p) {
+      rows_plan(p.a, Ma, rows, sl, nmat);
+      rows_plan(p.b, Mb, rows, sl, nmat);
+    },
+    [&](const BsgsPlan &p, uint64_t *pts) {
+      rows_encode(p.a, Ma, lvl, rows, sl, nmat, pts);
+      rows_encode(p.b, Mb, lvl, rows, sl, nmat, pts + p.a.ds.size() * pw);
+    });
 }
 
 // sl: the slots of one loop; it divides the context's (a power of two)
@@ -4153,149 +4041,47 @@ static void rows_check_loops(const char *who, unsigned sl)
 static void rows_genrk(const char *who, he_evk_t rk[], const poly_mpi_t *sk, unsigned sl, unsigned rows)
 {
   check_ctx();
-  const unsigned s = G.slots;
   rows_check_loops(who, sl);
   if (!rows || rows > sl)
     gpqhe_die("%s: rows = %u, slots = %u", who, rows, sl);
-  const unsigned mp = rows_pow2(rows), P = s / sl;
-  if (rk[0].data)
-    obj_free(&rk[0]);
-  rk[0].galois = 1;
-  for (unsigned r = 1; r < s; r++) {
+  const unsigned mp = rows_pow2(rows), P = G.slots / sl;
+  gen_rot_keys(rk, sk, [=](unsigned r) {
     const unsigned i = r / P;                                   // the loops' own rotation (r = i P)
     const bool fold = i % mp == 0 && !(i / mp & (i / mp - 1));  // m' 2^t
-    if (r % P == 0 && (i < mp || fold))
-      gen_rot_key(&rk[r], galois_of_rot(r), sk);
-    else if (rk[r].data)
-      he_free_evk(&rk[r]);
-  }
+    return r % P == 0 && (i < mp || fold);
+  });
 }
 
 extern "C" void he_genrk_rows(he_evk_t rk[], const poly_mpi_t *sk, unsigned int rows)
 {
-  check_ctx();
+  check_ctx();  // (G.slots is read here)
   rows_genrk("he_genrk_rows", rk, sk, G.slots, rows);
 }
 
 extern "C" void he_genrk_packed(he_evk_t rk[], const poly_mpi_t *sk, unsigned int s, unsigned int rows)
 {
-  check_ctx();
   rows_genrk("he_genrk_packed", rk, sk, s, rows);
-}
-
-// One chunk of cnt ciphertexts: ka / kb the baby rotations of each operand,
-// fold the rotations m', 2 m', .. < s.  st as in bsgs2_chunk; its tail is the
-// last fold step's kernel, or k_step_tail_batch where there is no fold.
-static void rows_chunk(uint64_t *y, const uint64_t *xa, const uint64_t *xb, const StepIn *st, unsigned cnt,
-                       unsigned lvl, const RowsPlan &plan, const BsgsKeys &ka, const BsgsKeys &kb,
-                       const std::vector<unsigned> &fold, const he_evk_t rk[], size_t budget)
-{
-  const size_t n = G.n, pw = (size_t)lvl * n, cw = 2 * pw, sw = (size_t)cnt * cw;  // words: ciphertext, slot
-  const size_t ow = 2 * (size_t)(lvl - 1) * n;                                     // ... of y
-  const unsigned nbs = ka.nbs + kb.nbs;
-  Ws B((size_t)nbs * sw), U(sw);
-  uint64_t *Ba = B.p, *Bb = B.p + (size_t)ka.nbs * sw;
-
-  Ws Xd(st && !ka.has0 ? sw : 0), Ud(st && !kb.has0 ? sw : 0);
-  if (st) {
-    uint64_t *xd = ka.has0 ? Ba : Xd.p, *ud = kb.has0 ? Bb : Ud.p;
-    k_step_diff_batch(xd, ud, st->xhat, st->xr, st->uhat, st->ur, lvl, cnt);
-    xa = xd;
-    xb = ud;
-  }
-
-  // baby rotations of both operands, the sum over all of their extended
-  // diagonals (one "giant step"), the rescale by q_top into y
-  const bool win = gemv_win_on(lvl);
-  bsgs2_baby(Ba, xa, cnt, lvl, ka, rk, budget, win);
-  bsgs2_baby(Bb, xb, cnt, lvl, kb, rk, budget, win);
-  k_bsgs_inner_batch(U.p, B.p, plan.pts, plan.tab_dev, 1, nbs, nbs, lvl, cnt);
-  k_moddown(y, (size_t)(lvl - 1) * n, U.p, pw, 2 * cnt, lvl, 2);
-
-  // the fold at level lvl - 1: the whole chunk rotated into R (the baby slots'
-  // buffer: the inner sums were the last to read it), then accumulated
-  uint64_t *R = B.p;
-  const bool winf = gemv_win_on(lvl - 1);
-  for (size_t t = 0; t < fold.size(); t++) {
-    if (winf) {
-      const RotFold &f = bsgs_rot_fold(fold[t], lvl - 1, rk);
-      RotFoldUse use(f);
-      k_gemv_batch(R, y, cnt, lvl - 1, f.K, &f.rot, 1, 0);
-    } else {
-      for (unsigned c = 0; c < cnt; c++) {
-        he_ct_t cx = ct_view(y + c * ow, lvl - 1), co = ct_view(R + c * ow, lvl - 1);
-        he_rot(&co, &cx, fold[t], rk);
-      }
-    }
-    if (st && t + 1 == fold.size())
-      k_rows_fold_tail_batch(y, R, st->uhat, lvl, cnt);
-    else
-      k_rows_fold_add_batch(y, R, lvl - 1, cnt);
-  }
-  if (st && fold.empty())
-    k_step_tail_batch(y, st->uhat, lvl, cnt);
 }
 
 static void rows_run(const char *who, uint64_t *y, const double *Ma, const double *Mb, const uint64_t *xa,
                      const uint64_t *xb, const StepIn *st, size_t count, unsigned lvl, const he_evk_t rk[],
                      unsigned rows, unsigned sl, unsigned nmat)
 {
-  check_ctx();
-  if (lvl < 2 || lvl > G.L)
-    gpqhe_die("%s: bad level %u", who, lvl);
-  rows_check_loops(who, sl);
-  const unsigned s = sl, P = G.slots / sl;  // s: the slots of one loop
-  if (!rows || rows > s)
-    gpqhe_die("%s: rows = %u, slots = %u", who, rows, s);
-  if (nmat != 1 && nmat != P)
-    gpqhe_die("%s: %u matrices for %u loops", who, nmat, P);
-  const unsigned nm = lvl + G.K, ndig = (lvl + G.alpha - 1) / G.alpha;
-  const size_t n = G.n, pw = (size_t)lvl * n, in_words = 2 * pw, out_words = 2 * (size_t)(lvl - 1) * n;
-  if (!count)
-    return;
-  const uint64_t *ins[4] = {st ? st->xhat : xa, st ? st->xr : xb, st ? st->uhat : nullptr, st ? st->ur : nullptr};
-  for (const uint64_t *x : ins)
-    if (x && y < x + count * in_words && x < y + count * out_words)
-      gpqhe_die("%s: output overlaps an input", who);
-
-  RowsPlanHold hold;
-  const RowsPlan *plan = rows_plan_get(hold, Ma, Mb, lvl, rows, sl, nmat);
-  if (plan->a.baby.empty() && plan->b.baby.empty()) {  // y = 0, up = the lower limbs of uhat
-    HIP_CHECK(hipMemsetAsync(y, 0, count * out_words * 8, G.stream));
-    for (size_t c0 = 0; st && c0 < count; c0 += 16384) {
-      const unsigned cnt = (unsigned)std::min<size_t>(16384, count - c0);
-      k_step_tail_batch(y + c0 * out_words, st->uhat + c0 * in_words, lvl, cnt);
-    }
-    return;
-  }
-  // every key is found before anything is launched
-  const BsgsKeys ka = bsgs_find_keys(plan->a, rk, 1), kb = bsgs_find_keys(plan->b, rk, 1);
-  std::vector<unsigned> fold;
-  for (unsigned r = rows_pow2(rows); r < s; r <<= 1) {
-    find_rot_key(rk, r * P, galois_of_rot(r * P));
-    fold.push_back(r * P);
-  }
-
-  // a ciphertext's share of a chunk, in words of one ciphertext (2 lvl n): the
-  // baby slots of both operands (later the rotated copy of the fold, which is
-  // smaller), the sum, and 1 per operand of a step whose difference has no
-  // slot 0 to live in; on the windowed path k_gemv_batch's workspace besides
-  const size_t budget = bsgs_budget();
-  const size_t slots_ct = ka.nbs + kb.nbs + 1 + (st ? !ka.has0 + !kb.has0 : 0);
-  const size_t per_ct =
-    slots_ct * 2 * pw + (gemv_win_on(lvl) ? ((size_t)lvl + (size_t)ndig * nm + 2 * (size_t)nm) * n : 0);
-  size_t chunk = std::min<size_t>(std::max<size_t>(1, budget / per_ct), 16384);
-  if (const char *e = getenv("GPQHE_BSGS_CHUNK"))  // test hook: several chunks on a small batch
-    chunk = std::max<size_t>(1, std::min<size_t>(chunk, strtoul(e, nullptr, 0)));
-  else  // equal chunks, as he_gemv_bsgs_batch
-    chunk = (count + (count + chunk - 1) / chunk - 1) / ((count + chunk - 1) / chunk);
-  for (size_t c0 = 0; c0 < count; c0 += chunk) {
-    const unsigned cnt = (unsigned)std::min(chunk, count - c0);
-    const size_t o = c0 * in_words;
-    const StepIn sc = st ? StepIn{st->xhat + o, st->xr + o, st->uhat + o, st->ur + o} : StepIn{};
-    rows_chunk(y + c0 * out_words, st ? nullptr : xa + o, st ? nullptr : xb + o, st ? &sc : nullptr, cnt, lvl, *plan,
-               ka, kb, fold, rk, budget);
-  }
+  bsgs_run(
+    who, y, xa, xb, st, count, lvl, rk,
+    [&] {
+      rows_check_loops(who, sl);
+      const unsigned P = G.slots / sl;
+      if (!rows || rows > sl)
+        gpqhe_die("%s: rows = %u, slots = %u", who, rows, sl);
+      if (nmat != 1 && nmat != P)
+        gpqhe_die("%s: %u matrices for %u loops", who, nmat, P);
+      BatchKind kind{1, {}};  // the fold: the rotations m' P, 2 m' P, .. < S
+      for (unsigned r = rows_pow2(rows); r < sl; r <<= 1)
+        kind.fold.push_back(r * P);
+      return kind;
+    },
+    [&](PlanHold &h) { return rows_plan_get(h, Ma, Mb, lvl, rows, sl, nmat); });
 }
 
 extern "C" void he_gemv2_rows_batch(uint64_t *y, const gpqhe_complex_t Ma[], const uint64_t *xa,
@@ -4303,7 +4089,7 @@ extern "C" void he_gemv2_rows_batch(uint64_t *y, const gpqhe_complex_t Ma[], con
                                     const he_evk_t rk[], unsigned int rows)
 {
   HPROF("gemv2_rows_batch");
-  check_ctx();
+  check_ctx();  // (G.slots is read here)
   rows_run("he_gemv2_rows_batch", y, (const double *)Ma, (const double *)Mb, xa, xb, nullptr, count, nlimbs, rk, rows,
            G.slots, 1);
 }
@@ -4315,7 +4101,7 @@ extern "C" void he_hempc_step_rows_batch(uint64_t *up, const gpqhe_complex_t Ma[
 {
   HPROF("hempc_step_rows_batch");
   const StepIn st{xhat, xr, uhat, ur};
-  check_ctx();
+  check_ctx();  // (G.slots is read here)
   rows_run("he_hempc_step_rows_batch", up, (const double *)Ma, (const double *)Mb, nullptr, nullptr, &st, count, nlimbs,
            rk, rows, G.slots, 1);
 }

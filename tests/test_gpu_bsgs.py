@@ -171,12 +171,15 @@ def test_workspace_chunks_do_not_change_bits(oracle, product, g, monkeypatch):
 def test_small_diagonal_cache():
     """GPQHE_DIAG_MIB = 1 (read once per process, so a process of its own):
     a set larger than the cap is encoded into workspace on every call, and
-    three matrices rotate through a cache that holds two (tests/bsgs_cache_worker.py)."""
+    three plans rotate through a cache that holds two -- in each of the three
+    plan caches (he_gemv_bsgs, he_gemv2_bsgs_batch, he_gemv2_rows_batch), their
+    calls interleaved (tests/bsgs_cache_worker.py)."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "tests", "bsgs_cache_worker.py")],
                        env=dict(os.environ, GPQHE_DIAG_MIB="1"), cwd=root, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, f"rc {r.returncode}\n" + r.stdout[-2000:] + r.stderr[-3000:]
-    assert json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1]) == {"ok": True, "calls": 12}
+    assert json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1]) == {
+        "ok": True, "calls": {"bsgs": 12, "pair": 12, "rows": 12}}
 
 
 # --------------------------------------------------------------------- state
