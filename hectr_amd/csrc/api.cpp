@@ -4342,6 +4342,170 @@ extern "C" void he_dec_dcd_packed_batch(gpqhe_complex_t z[], const uint64_t *y, 
   dec_dcd_run("he_dec_dcd_packed_batch", z, y, count, nlimbs, scale, G.slots, sk, P == 1 && rows == s ? 0 : P, rows);
 }
 
+// ---------------------------------------------------------------------------
+// he_enc_gain_packed_batch / he_gemv2_encgain_packed_batch /
+// he_hempc_step_encgain_packed_batch (include/gpqhe_ext_encgain_batch.h): the
+// packed row-folded step whose 2 m' extended diagonals arrive encrypted.  The
+// products are ciphertext x ciphertext, but their tensor terms are summed
+// before anything else happens to them (encgain_batch.hip), so a ciphertext
+// costs 2 (m' - 1) baby rotations, one rescale of the linear part, ONE
+// relinearisation of the summed quadratic part (mul_chunk on (0, X2) x (0, 1):
+// its tensor is (0, 0, X2)) and the fold: one key switch more than the packed
+// step, whatever m'.  Nothing is encoded, so there is no plan.
+// ---------------------------------------------------------------------------
+extern "C" void he_enc_gain_packed_batch(uint64_t *D, const gpqhe_complex_t M[], unsigned int s, unsigned int rows,
+                                         unsigned int nmat, unsigned int nlimbs, const he_pk_t *pk)
+{
+  HPROF("enc_gain_packed_batch");
+  const char *who = "he_enc_gain_packed_batch";
+  check_ctx();
+  const unsigned P = packed_loops(who, s);
+  if (!rows || rows > s)
+    gpqhe_die("%s: rows = %u, s = %u", who, rows, s);
+  if (nmat != 1 && nmat != P)
+    gpqhe_die("%s: %u matrices for %u loops", who, nmat, P);
+  io_check(who, nlimbs, G.slots);
+  if (!M)
+    gpqhe_die("%s: null argument", who);
+  // every E_i, the all-zero ones too: which diagonals vanish stays with the client
+  const unsigned mp = rows_pow2(rows);
+  std::vector<double> E(2 * (size_t)mp * G.slots), v(2 * (size_t)G.slots);
+  for (unsigned i = 0; i < mp; i++) {
+    rows_diag(v, (const double *)M, i, rows, mp, s, nmat);
+    std::copy(v.begin(), v.end(), E.begin() + 2 * (size_t)i * G.slots);
+  }
+  enc_pk_run(who, D, (const gpqhe_complex_t *)E.data(), mp, G.slots, (double)G.q[nlimbs - 1], nlimbs, pk, 0, 0);
+}
+
+// One chunk of cnt ciphertexts.  W: 2 (m' - 1) + 3 (+ 2 with st) slots of cnt
+// ciphertexts at level lvl -- the rotated inputs, then X01 (later quad), Q
+// (0, X2), the ones (later the fold's rotated copy), then the step's two
+// differences.
+static void encgain_chunk(uint64_t *y, const uint64_t *DA, const uint64_t *DB, const uint64_t *xa, const uint64_t *xb,
+                          const StepIn *st, unsigned cnt, unsigned lvl, unsigned mp, const BsgsKeys &kb,
+                          const std::vector<unsigned> &fold, const he_evk_t rk[], const he_evk_t *rlk, size_t budget)
+{
+  const size_t n = G.n, pw = (size_t)lvl * n, cw = 2 * pw, sw = (size_t)cnt * cw;
+  const size_t ow = 2 * (size_t)(lvl - 1) * n;
+  Ws W((2 * (size_t)(mp - 1) + 3 + (st ? 2 : 0)) * sw);
+  uint64_t *Ra = W.p, *Rb = Ra + (mp - 1) * sw, *X01 = Rb + (mp - 1) * sw, *Q = X01 + sw, *one = Q + sw;
+  if (st) {
+    uint64_t *xd = one + sw, *ud = xd + sw;
+    k_step_diff_batch(xd, ud, st->xhat, st->xr, st->uhat, st->ur, lvl, cnt);
+    xa = xd;
+    xb = ud;
+  }
+  // the baby rotations i P, 1 <= i < m', of each operand
+  bsgs_baby_chunk(Ra, xa, cnt, lvl, kb, rk, budget);
+  bsgs_baby_chunk(Rb, xb, cnt, lvl, kb, rk, budget);
+  k_encgain_tensor(X01, Q, xa, xb, Ra, Rb, DA, DB, mp, lvl, cnt);
+  // lin: the rescale of (X0, X1) into y; quad: (0, X2) x (0, 1) relinearised
+  // and rescaled into X01's place, which the rescale has read
+  k_moddown(y, (size_t)(lvl - 1) * n, X01, pw, 2 * cnt, lvl, 2);
+  k_encgain_ones(one, lvl, cnt);
+  uint64_t *quad = X01, *R = one;
+  mul_chunk(quad, (size_t)(lvl - 1) * n, Q, one, cw, pw, cnt, lvl, rlk, true);
+  k_rows_fold_add_batch(y, quad, lvl - 1, cnt);
+  // the fold at level lvl - 1 and the step's tail, as bsgs_chunk's
+  for (size_t t = 0; t < fold.size(); t++) {
+    if (gemv_win_on(lvl - 1)) {
+      win_rot_chunk(R, y, 0, &fold[t], 1, cnt, lvl - 1, rk);
+    } else {
+      for (unsigned c = 0; c < cnt; c++) {
+        he_ct_t cx = ct_view(y + c * ow, lvl - 1), co = ct_view(R + c * ow, lvl - 1);
+        he_rot(&co, &cx, fold[t], rk);
+      }
+    }
+    if (st && t + 1 == fold.size())
+      k_rows_fold_tail_batch(y, R, st->uhat, lvl, cnt);
+    else
+      k_rows_fold_add_batch(y, R, lvl - 1, cnt);
+  }
+  if (st && fold.empty())
+    k_step_tail_batch(y, st->uhat, lvl, cnt);
+}
+
+// The run of both cloud-side entry points: argument checks, then keys, then
+// the first launch.
+static void encgain_run(const char *who, uint64_t *y, const uint64_t *DA, const uint64_t *DB, const uint64_t *xa,
+                        const uint64_t *xb, const StepIn *st, size_t count, unsigned lvl, const he_evk_t rk[],
+                        const he_evk_t *rlk, unsigned sl, unsigned rows)
+{
+  check_ctx();
+  if (lvl < 2 || lvl > G.L)
+    gpqhe_die("%s: bad level %u", who, lvl);
+  const unsigned P = packed_loops(who, sl);
+  if (!rows || rows > sl)
+    gpqhe_die("%s: rows = %u, slots = %u", who, rows, sl);
+  if (!rlk || !rlk->data || rlk->dnum != G.dnum)
+    gpqhe_die("%s: relinearization key missing or built for another dnum", who);
+  const unsigned mp = rows_pow2(rows), nm = lvl + G.K, ndig = (lvl + G.alpha - 1) / G.alpha;
+  const size_t n = G.n, pw = (size_t)lvl * n, in_words = 2 * pw, out_words = 2 * (size_t)(lvl - 1) * n;
+  if (!count)
+    return;
+  if (!y || !DA || !DB)
+    gpqhe_die("%s: null argument", who);
+  const uint64_t *ins[4] = {st ? st->xhat : xa, st ? st->xr : xb, st ? st->uhat : nullptr, st ? st->ur : nullptr};
+  for (const uint64_t *x : ins)
+    if (x && y < x + count * in_words && x < y + count * out_words)
+      gpqhe_die("%s: output overlaps an input", who);
+  for (const uint64_t *d : {DA, DB})
+    if (y < d + mp * in_words && d < y + count * out_words)
+      gpqhe_die("%s: output overlaps a diagonal", who);
+
+  // every key is found before anything is launched
+  std::vector<unsigned> baby, fold;
+  for (unsigned i = 1; i < mp; i++)
+    baby.push_back(i * P);
+  for (unsigned r = mp; r < sl; r <<= 1)
+    fold.push_back(r * P);
+  const BsgsKeys kb = bsgs_find_keys(baby, {}, 1, rk);
+  for (unsigned r : fold)
+    find_rot_key(rk, r, galois_of_rot(r));
+
+  // a ciphertext's share of a chunk: the slots of encgain_chunk, and the larger
+  // of the multiply's workspace (he_mul_rescale_batch's count) and, on the
+  // windowed path, k_gemv_batch's
+  const size_t budget = bsgs_budget();
+  const size_t mul_ws = k_mul_split_ok(lvl) ? (size_t)lvl + (size_t)ndig * nm + 2 * (G.K + 1) + 2 * (size_t)lvl
+                                            : 6 * (size_t)lvl + (size_t)ndig * nm + 2 * (size_t)nm;
+  const size_t rot_ws = gemv_win_on(lvl) ? (size_t)lvl + (size_t)ndig * nm + 2 * (size_t)nm : 0;
+  const size_t per_ct = (2 * (size_t)(mp - 1) + 3 + (st ? 2 : 0)) * 2 * pw + std::max(mul_ws, rot_ws) * n;
+  size_t chunk = std::min<size_t>(std::max<size_t>(1, budget / per_ct), 16384);
+  chunk = std::min<size_t>(chunk, 65535 / (ndig * nm));  // (the multiply's launch grid)
+  if (const char *e = getenv("GPQHE_BSGS_CHUNK"))  // test hook: several chunks on a small batch
+    chunk = std::max<size_t>(1, std::min<size_t>(chunk, strtoul(e, nullptr, 0)));
+  else  // equal chunks: a short last one runs at a fraction of the GPU's width
+    chunk = (count + (count + chunk - 1) / chunk - 1) / ((count + chunk - 1) / chunk);
+  for (size_t c0 = 0; c0 < count; c0 += chunk) {
+    const unsigned cnt = (unsigned)std::min(chunk, count - c0);
+    const size_t o = c0 * in_words;
+    const StepIn sc = st ? StepIn{st->xhat + o, st->xr + o, st->uhat + o, st->ur + o} : StepIn{};
+    encgain_chunk(y + c0 * out_words, DA, DB, st ? nullptr : xa + o, st ? nullptr : xb + o, st ? &sc : nullptr, cnt,
+                  lvl, mp, kb, fold, rk, rlk, budget);
+  }
+}
+
+extern "C" void he_gemv2_encgain_packed_batch(uint64_t *y, const uint64_t *DA, const uint64_t *xa, const uint64_t *DB,
+                                              const uint64_t *xb, size_t count, unsigned int nlimbs,
+                                              const he_evk_t rk[], const he_evk_t *rlk, unsigned int s,
+                                              unsigned int rows)
+{
+  HPROF("gemv2_encgain_packed_batch");
+  encgain_run("he_gemv2_encgain_packed_batch", y, DA, DB, xa, xb, nullptr, count, nlimbs, rk, rlk, s, rows);
+}
+
+extern "C" void he_hempc_step_encgain_packed_batch(uint64_t *up, const uint64_t *DA, const uint64_t *DB,
+                                                   const uint64_t *xhat, const uint64_t *xr, const uint64_t *uhat,
+                                                   const uint64_t *ur, size_t count, unsigned int nlimbs,
+                                                   const he_evk_t rk[], const he_evk_t *rlk, unsigned int s,
+                                                   unsigned int rows)
+{
+  HPROF("hempc_step_encgain_packed_batch");
+  const StepIn st{xhat, xr, uhat, ur};
+  encgain_run("he_hempc_step_encgain_packed_batch", up, DA, DB, nullptr, nullptr, &st, count, nlimbs, rk, rlk, s, rows);
+}
+
 // groups of ~224 MiB (ntt_batch), at most 65535 limbs a launch
 static size_t ntt_group_polys(unsigned nlimbs)
 {

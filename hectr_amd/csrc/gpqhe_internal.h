@@ -479,7 +479,7 @@ enum KClass {
   KC_BSGS_SUM, KC_BSGS_INNER_BATCH, KC_BSGS_SUM_BATCH, KC_FFT_ENC_BATCH, KC_ENC_SAMPLE_BATCH, KC_ENC_COMBINE_BATCH,
   KC_DEC_FOLD, KC_FOLD_DCD, KC_DEC_BATCH, KC_STEP_DIFF_BATCH, KC_STEP_TAIL_BATCH,
   KC_ROWS_FOLD_ADD_BATCH, KC_ROWS_FOLD_TAIL_BATCH, KC_PACK_ENC_GATHER, KC_PACK_DCD_GATHER, KC_FOLD_DCD_PACKED,
-  KC_FFT_DEC_PACKED, KC_COUNT
+  KC_FFT_DEC_PACKED, KC_ENCGAIN_TENSOR, KC_ENCGAIN_ONES, KC_COUNT
 };
 struct ProfScope {
   int cls;
@@ -597,6 +597,17 @@ void k_decode_packed(double *z, const uint64_t *coef, unsigned nl, unsigned S, d
                      unsigned rows);
 void k_fold_decode_packed(double *z, uint64_t *D, const uint64_t *F, unsigned nl, unsigned S, double scale,
                           unsigned cnt, unsigned P, unsigned rows);
+// he_gemv2_encgain_packed_batch / he_hempc_step_encgain_packed_batch
+// (encgain_batch.hip) over a chunk of cnt ciphertexts: the tensor sums of the
+// 2 mp pairs (rot(xa, i P), DA_i), (rot(xb, i P), DB_i), i < mp.  xa, xb
+// [cnt][2][lvl][n] (rotation 0), Ra, Rb [mp - 1][cnt][2][lvl][n] (rotation i in
+// slot i - 1; unread for mp = 1), DA, DB [mp][2][lvl][n].  X01 [cnt][2][lvl][n]
+// <- (X0, X1), Q [cnt][2][lvl][n] <- (0, X2); neither overlaps an input.
+void k_encgain_tensor(uint64_t *X01, uint64_t *Q, const uint64_t *xa, const uint64_t *xb, const uint64_t *Ra,
+                      const uint64_t *Rb, const uint64_t *DA, const uint64_t *DB, unsigned mp, unsigned lvl,
+                      unsigned cnt);
+// one [cnt][2][lvl][n] <- the ciphertext (0, 1) of every pair
+void k_encgain_ones(uint64_t *one, unsigned lvl, unsigned cnt);
 void tables_upload();
 void tables_prewarm();
 void tables_free();

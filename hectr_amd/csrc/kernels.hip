@@ -53,7 +53,7 @@ static const char *kc_names[KC_COUNT] = {
   "fft_enc_batch_kernel", "enc_sample_batch_kernel", "enc_combine_batch_kernel", "dec_fold_kernel",
   "fold_dcd_kernel", "dec_batch_kernel", "step_diff_batch_kernel", "step_tail_batch_kernel",
   "rows_fold_add_batch_kernel", "rows_fold_tail_batch_kernel", "pack_enc_gather_kernel", "pack_dcd_gather_kernel",
-  "fold_dcd_packed_kernel", "fft_dec_lds_packed_kernel"};
+  "fold_dcd_packed_kernel", "fft_dec_lds_packed_kernel", "encgain_tensor_kernel", "encgain_ones_kernel"};
 
 struct ProfEntry {
   int cls;

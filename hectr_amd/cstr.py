@@ -573,3 +573,50 @@ class PackedEncryptedRegulator:
         e.free(self.sk)
         e.free_evks(self.rk)
         self.x = self.up = None
+
+
+class EncryptedGainRegulator(PackedEncryptedRegulator):
+    """PackedEncryptedRegulator's loop with the gains hidden from the machine
+    that runs it (include/gpqhe_ext_encgain_batch.h): after the keys, the
+    constructor makes the relinearisation key and encrypts the m' extended
+    diagonals of MA and of MB once (he_enc_gain_packed_batch, MA first); every
+    step is he_hempc_step_encgain_packed_batch on those two ciphertext sets.
+    Packing, keys, encryption and decode are the parent's."""
+
+    def __init__(self, engine, problems, slots_total, rows=None, seed=None, logn=12, logq=109, log_delta=50,
+                 init=True):
+        import torch
+        super().__init__(engine, problems, slots_total, rows, seed, logn, logq, log_delta, init)
+        self.rlk = engine.evk()
+        engine.genrlk(self.rlk, self.sk)
+        mp = 1
+        while mp < self.rows:
+            mp <<= 1
+        self.mp = mp
+        self.D = torch.zeros(2 * mp * self.cw, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        self.DA, self.DB = self.D.data_ptr(), self.D.data_ptr() + 8 * mp * self.cw
+        engine.enc_gain_packed_batch(self.DA, self.MAz, self.pk, self.s, self.rows, self.lvl, self.nmat)
+        engine.enc_gain_packed_batch(self.DB, self.MBz, self.pk, self.s, self.rows, self.lvl, self.nmat)
+
+    def __call__(self, xhat, uhat, xr, ur):
+        e, cnt, P, w = self.e, self.count, self.P, self.width
+        t0 = time.perf_counter()
+        zs = np.zeros((4, cnt * P, w), dtype=np.complex128)
+        for b, v in enumerate((xhat, xr, uhat, ur)):
+            v = np.asarray(v, dtype=np.float64).reshape(self.nloops, -1)
+            zs[b, :self.nloops, :v.shape[1]] = v
+        e.enc_pk_packed_batch(self.x.data_ptr(), zs.reshape(4 * cnt, P, w), self.pk, self.s, w, self.scale, self.lvl)
+        part = [self.x.data_ptr() + 8 * b * cnt * self.cw for b in range(4)]
+        e.hempc_step_encgain_packed_batch(self.up.data_ptr(), self.DA, self.DB, part[0], part[1], part[2], part[3],
+                                          cnt, self.lvl, self.rk, self.rlk, self.s, self.rows)
+        uz = e.dec_dcd_packed_batch(self.up.data_ptr(), cnt, self.lvl - 1, self.scale, self.sk, self.s, self.rows)
+        assert np.all(uz.imag < HECTR_SMALL), "imaginary part too large (src/ctr.c:493-494)"
+        self.timings.append(time.perf_counter() - t0)
+        return uz.real.reshape(cnt * P, self.rows)[:self.nloops, :self.problems[0].nu].copy()
+
+    def close(self):
+        self.e.sync()
+        self.e.free(self.rlk)
+        self.D = None
+        super().close()

@@ -197,6 +197,15 @@ PRODUCT_EXT_PACKED_BATCH = {
     "he_dec_dcd_packed_batch": (None, [VP, VP, C.c_size_t, C.c_uint, C.c_double, C.c_uint, C.c_uint, OBJ]),
 }
 
+#: include/gpqhe_ext_encgain_batch.h (part of gpqhe_ext_batch.h): the packed
+#: step with encrypted gains, product only, bound like PRODUCT_EXT
+PRODUCT_EXT_ENCGAIN_BATCH = {
+    "he_enc_gain_packed_batch": (None, [VP, VP, C.c_uint, C.c_uint, C.c_uint, C.c_uint, OBJ]),
+    "he_gemv2_encgain_packed_batch": (None, [VP, VP, VP, VP, VP, C.c_size_t, C.c_uint, OBJ, OBJ, C.c_uint, C.c_uint]),
+    "he_hempc_step_encgain_packed_batch": (None, [VP, VP, VP, VP, VP, VP, VP, C.c_size_t, C.c_uint, OBJ, OBJ,
+                                                  C.c_uint, C.c_uint]),
+}
+
 
 def _cplx(z) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(z, dtype=np.complex128))
@@ -220,7 +229,7 @@ class Engine:
             f.argtypes = args
         for sym, (res, args) in {**PRODUCT_EXT, **PRODUCT_EXT_BATCH, **PRODUCT_EXT_IO_BATCH,
                                  **PRODUCT_EXT_STEP_BATCH, **PRODUCT_EXT_ROWS_BATCH,
-                                 **PRODUCT_EXT_PACKED_BATCH}.items():
+                                 **PRODUCT_EXT_PACKED_BATCH, **PRODUCT_EXT_ENCGAIN_BATCH}.items():
             if hasattr(self.lib, sym):  # not the oracle, nor an older library under GPQHE_LIB
                 f = getattr(self.lib, sym)
                 f.restype = res
@@ -459,6 +468,33 @@ class Engine:
         z = np.zeros((count, self.slots // s, rows), dtype=np.complex128)
         f(z.ctypes.data, y_ptr, count, nlimbs, scale, s, rows, C.byref(sk))
         return z
+
+    def enc_gain_packed_batch(self, d_ptr, M, pk, s, rows, nlimbs, nmat=1):
+        """The client's half of the step with encrypted gains: all m' =
+        2^ceil(log2 rows) extended diagonals of M [nmat][rows][s], the zero ones
+        too, encrypted at scale q_top into device memory d_ptr
+        [m'][2][nlimbs][n] (include/gpqhe_ext_encgain_batch.h)."""
+        f = self._ext("he_enc_gain_packed_batch")
+        M = _cplx(M)
+        assert M.size >= nmat * rows * s
+        f(d_ptr, M.ctypes.data, s, rows, nmat, nlimbs, C.byref(pk))
+
+    def gemv2_encgain_packed_batch(self, y_ptr, da_ptr, xa_ptr, db_ptr, xb_ptr, count, nlimbs, rk, rlk, s, rows):
+        """gemv2_packed_batch with the gains as enc_gain_packed_batch left them
+        (da_ptr, db_ptr [m'][2][nlimbs][n]): ciphertext x ciphertext, one
+        relinearisation under rlk per ciphertext; xa_ptr, xb_ptr
+        [count][2][nlimbs][n] -> y_ptr [count][2][nlimbs-1][n], device memory
+        (include/gpqhe_ext_encgain_batch.h)."""
+        f = self._ext("he_gemv2_encgain_packed_batch")
+        f(y_ptr, da_ptr, xa_ptr, db_ptr, xb_ptr, count, nlimbs, rk, C.byref(rlk), s, rows)
+
+    def hempc_step_encgain_packed_batch(self, up_ptr, da_ptr, db_ptr, xhat_ptr, xr_ptr, uhat_ptr, ur_ptr, count,
+                                        nlimbs, rk, rlk, s, rows):
+        """hempc_step_packed_batch with encrypted gains; four inputs
+        [count][2][nlimbs][n] -> up_ptr [count][2][nlimbs-1][n], device memory
+        (include/gpqhe_ext_encgain_batch.h)."""
+        f = self._ext("he_hempc_step_encgain_packed_batch")
+        f(up_ptr, da_ptr, db_ptr, xhat_ptr, xr_ptr, uhat_ptr, ur_ptr, count, nlimbs, rk, C.byref(rlk), s, rows)
 
     def enc_pk_batch(self, x_ptr, zs, pk, slots, scale, nlimbs):
         """he_ecd_ex + he_enc_pk of the rows of zs [count][slots] into device
