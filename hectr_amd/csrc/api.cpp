@@ -98,24 +98,29 @@ struct Ws {
   Ws &operator=(const Ws &) = delete;
 };
 
-// Folded gemv / rotation keys (see gemv_fold below).
+// Folded gemv / rotation keys (see the fold caches below).
 static uint64_t g_key_gen = 1;
-struct FoldEntry {
-  std::vector<double> M;  // the matrix (he_gemv); empty for a rotation
-  unsigned s, lvl, rot;
+struct FoldEntry {  // a matrix of he_gemv
+  std::vector<double> M;
+  unsigned s, lvl;
   uint64_t gen;
   const he_evk_t *rk;
   std::vector<unsigned> d;  // rotation of each folded diagonal
   double *K;
   size_t bytes;
 };
-// (a list: a caller's reference to its entry survives the eviction of others)
-static std::list<FoldEntry> g_folds;
-static const double *g_fold_inuse = nullptr;  // the set a running call reads
-// While a call reads a folded set, an out-of-memory retry inside it keeps
-// that set (fold_cache_trim).
+struct RotFold {  // one rotation key
+  const he_evk_t *rk;
+  uint64_t gen;
+  unsigned lvl, rot;
+  double *K;
+  size_t bytes;
+};
+// While a call reads a folded set of either kind, an out-of-memory retry
+// inside it keeps that set (fold_cache_trim).
+static const double *g_fold_inuse = nullptr;
 struct FoldUse {
-  explicit FoldUse(const FoldEntry &f) { g_fold_inuse = f.K; }
+  explicit FoldUse(const double *K) { g_fold_inuse = K; }
   ~FoldUse() { g_fold_inuse = nullptr; }
 };
 
@@ -123,7 +128,7 @@ static void fold_cache_clear();
 static bool gemv_fold_fits(const double *Md, unsigned lvl, const he_evk_t rk[]);
 static bool gemv_win_on(unsigned lvl);
 static const FoldEntry &gemv_fold(const double *Md, unsigned lvl, const he_evk_t rk[]);
-static const FoldEntry &rot_fold(unsigned r, unsigned lvl, const he_evk_t rk[]);
+static const RotFold &rotkey_fold(unsigned r, unsigned lvl, const he_evk_t rk[]);
 
 // he_gemv's encoded diagonals, cached by content (the caller recomputes the
 // same gain matrices every control step: reference src/hempc.c:232-238), and
@@ -2370,10 +2375,10 @@ extern "C" void he_rot(he_ct_t *out, const he_ct_t *in, unsigned int rot, const 
   const uint64_t g = galois_of_rot(rot);
   const he_evk_t *k = find_rot_key(rk, rot, g);
   if (gemv_win_on(lvl)) {  // (reads every input word before the ModDown writes out: in place is fine)
-    const FoldEntry &f = rot_fold(rot, lvl, rk);
-    FoldUse use(f);
+    const RotFold &f = rotkey_fold(rot, lvl, rk);
+    FoldUse use(f.K);
     const double scale = in->scale;
-    k_gemv_batch_ex(out->data, 0, pstride(out), in->data, 0, pstride(in), 1, lvl, f.K, f.d.data(), 1, 0);
+    k_gemv_batch_ex(out->data, 0, pstride(out), in->data, 0, pstride(in), 1, lvl, f.K, &f.rot, 1, 0);
     out->nlimbs = lvl;
     out->scale = scale;
     out->flags = 0;
@@ -2746,7 +2751,7 @@ static bool gemv_folded(he_ct_t *y, const double *Md, const he_ct_t *x, const he
   check_ctx();
   prov_forget(y->data, pstride(y));
   const FoldEntry &f = gemv_fold(Md, lvl, rk);
-  FoldUse use(f);
+  FoldUse use(f.K);
   k_gemv_batch_ex(y->data, 0, pstride(y), x->data, 0, pstride(x), 1, lvl, f.K, f.d.data(), (unsigned)f.d.size(), 1);
   gemv_set_meta(y, x, lvl);
   return true;
@@ -3420,77 +3425,59 @@ static size_t fold_cap()
   return cap;
 }
 
-// The folded rotation keys of he_gemv_bsgs_batch: one entry per (key array,
-// key generation, level, rotation), most recently used first, bounded in
-// bytes by fold_cap() -- a cache apart from g_folds, whose eight entries a
-// BSGS call's 30 rotations would turn over on every call.  A call holds an
-// entry only while the launches that read it are issued (RotFoldUse).
-struct RotFold {
-  const he_evk_t *rk;
-  uint64_t gen;
-  unsigned lvl, rot;
-  double *K;
-  size_t bytes;
-};
+// Two lists.  g_folds: the matrices of he_gemv, newest first, at most eight
+// entries and fold_cap() bytes (a 16-slot gemv at N=2^16, L=8 folds to 480
+// MB).  g_rfolds: single rotation keys, one entry per (key array, key
+// generation, level, rotation), most recently used first, at most fold_cap()
+// bytes -- every windowed rotation looks its key up here (rotkey_fold): he_rot,
+// he_rot_batch and the BSGS, rows, packed and encrypted-gain products, whose
+// 30 rotations a call would turn eight entries over.  Each list has
+// fold_cap() to itself.  Entries of an older key generation never match and
+// leave at the list's next insert; a caller holds an entry only while the
+// launches that read it are issued (FoldUse).
+// (lists: a caller's reference to its entry survives the eviction of others)
+static std::list<FoldEntry> g_folds;
 static std::list<RotFold> g_rfolds;
-static size_t g_rfold_bytes = 0;
-static const double *g_rfold_inuse = nullptr;
-struct RotFoldUse {
-  explicit RotFoldUse(const RotFold &f) { g_rfold_inuse = f.K; }
-  ~RotFoldUse() { g_rfold_inuse = nullptr; }
-};
+
+// Releases the entries drop() names; the bytes of those that stay.
+template <class List, class Drop> static size_t fold_drop(List &l, Drop drop)
+{
+  size_t kept = 0;
+  for (auto it = l.begin(); it != l.end();)
+    if (drop(*it)) {
+      pool_free(it->K);
+      it = l.erase(it);
+    } else {
+      kept += it->bytes;
+      ++it;
+    }
+  return kept;
+}
+
+// Room for an entry of `bytes` in a list of at most max_entries: the entries
+// folded with keys that changed since go, then the list's last ones (the
+// oldest of g_folds, the least recently used of g_rfolds).
+template <class List> static void fold_make_room(List &l, size_t bytes, size_t max_entries)
+{
+  size_t total = bytes + fold_drop(l, [](const auto &f) { return f.gen != g_key_gen; });
+  while (!l.empty() && (l.size() >= max_entries || total > fold_cap())) {
+    total -= l.back().bytes;
+    pool_free(l.back().K);
+    l.pop_back();
+  }
+}
 
 static void fold_cache_clear()
 {
-  for (FoldEntry &f : g_folds)
-    pool_free(f.K);
-  g_folds.clear();
-  for (RotFold &f : g_rfolds)
-    pool_free(f.K);
-  g_rfolds.clear();
-  g_rfold_bytes = 0;
+  fold_drop(g_folds, [](const FoldEntry &) { return true; });
+  fold_drop(g_rfolds, [](const RotFold &) { return true; });
 }
 
 // out of memory: every set no running call reads goes back to the pool
 static void fold_cache_trim()
 {
-  for (auto it = g_folds.begin(); it != g_folds.end();)
-    if (it->K != g_fold_inuse) {
-      pool_free(it->K);
-      it = g_folds.erase(it);
-    } else {
-      ++it;
-    }
-  for (auto it = g_rfolds.begin(); it != g_rfolds.end();)
-    if (it->K != g_rfold_inuse) {
-      pool_free(it->K);
-      g_rfold_bytes -= it->bytes;
-      it = g_rfolds.erase(it);
-    } else {
-      ++it;
-    }
-}
-
-static const FoldEntry &fold_insert(FoldEntry &&f)
-{
-  // a few sets (a 16-slot gemv at N=2^16, L=8 folds to 480 MB); f.bytes is
-  // within the cap (gemv_fold_fits)
-  size_t total = f.bytes;
-  for (auto it = g_folds.begin(); it != g_folds.end();)
-    if (it->gen != g_key_gen) {  // folded with keys that changed since
-      pool_free(it->K);
-      it = g_folds.erase(it);
-    } else {
-      total += it->bytes;
-      ++it;
-    }
-  while (!g_folds.empty() && (g_folds.size() >= 8 || total > fold_cap())) {
-    total -= g_folds.front().bytes;
-    pool_free(g_folds.front().K);
-    g_folds.pop_front();
-  }
-  g_folds.push_back(std::move(f));
-  return g_folds.back();
+  fold_drop(g_folds, [](const FoldEntry &f) { return f.K != g_fold_inuse; });
+  fold_drop(g_rfolds, [](const RotFold &f) { return f.K != g_fold_inuse; });
 }
 
 static bool gemv_win_on(unsigned lvl)
@@ -3504,7 +3491,7 @@ static const FoldEntry *fold_find(const double *Md, unsigned lvl, const he_evk_t
   const unsigned s = G.slots;
   const size_t mwords = 2 * (size_t)s * s;
   for (const FoldEntry &f : g_folds)
-    if (!f.M.empty() && f.s == s && f.lvl == lvl && f.gen == g_key_gen && f.rk == rk &&
+    if (f.s == s && f.lvl == lvl && f.gen == g_key_gen && f.rk == rk &&
         !memcmp(f.M.data(), Md, mwords * 8))
       return &f;
   return nullptr;
@@ -3548,22 +3535,29 @@ static const FoldEntry &gemv_fold(const double *Md, unsigned lvl, const he_evk_t
     dg[e].pt = pts.p + e * per;
     dg[e].evk = ds[e] ? find_rot_key(rk, ds[e], galois_of_rot(ds[e]))->data : nullptr;
   }
-  FoldEntry f{std::vector<double>(Md, Md + mwords), s, lvl, 0, g_key_gen, rk, ds, nullptr,
+  FoldEntry f{std::vector<double>(Md, Md + mwords), s, lvl, g_key_gen, rk, ds, nullptr,
               k_gemv_fold_words(E, lvl) * 8};
   f.K = E ? k_gemv_fold(dg.data(), E, lvl) : nullptr;
-  return fold_insert(std::move(f));
+  fold_make_room(g_folds, f.bytes, 8);  // (f.bytes is within the cap: gemv_fold_fits)
+  g_folds.push_front(std::move(f));
+  return g_folds.front();
 }
 
-static const FoldEntry &rot_fold(unsigned r, unsigned lvl, const he_evk_t rk[])
+// The key of rotation r folded for level lvl.
+static const RotFold &rotkey_fold(unsigned r, unsigned lvl, const he_evk_t rk[])
 {
   const he_evk_t *k = find_rot_key(rk, r, galois_of_rot(r));
-  for (const FoldEntry &f : g_folds)
-    if (f.M.empty() && f.rot == r && f.lvl == lvl && f.gen == g_key_gen && f.rk == rk)
-      return f;
+  for (auto it = g_rfolds.begin(); it != g_rfolds.end(); ++it)
+    if (it->rot == r && it->lvl == lvl && it->gen == g_key_gen && it->rk == rk) {
+      g_rfolds.splice(g_rfolds.begin(), g_rfolds, it);
+      return g_rfolds.front();
+    }
+  const size_t bytes = k_gemv_fold_words(1, lvl) * 8;
+  fold_make_room(g_rfolds, bytes, SIZE_MAX);
   const GemvDiagIn dg{r, nullptr, k->data};
-  FoldEntry f{{}, G.slots, lvl, r, g_key_gen, rk, {r}, nullptr, k_gemv_fold_words(1, lvl) * 8};
-  f.K = k_gemv_fold(&dg, 1, lvl);
-  return fold_insert(std::move(f));
+  double *K = k_gemv_fold(&dg, 1, lvl);  // (an out-of-memory retry inside may empty the list)
+  g_rfolds.push_front(RotFold{rk, g_key_gen, lvl, r, K, bytes});
+  return g_rfolds.front();
 }
 
 static bool gemv_batch_fast(uint64_t *y, const double *Md, const uint64_t *x, size_t count, unsigned lvl,
@@ -3572,7 +3566,7 @@ static bool gemv_batch_fast(uint64_t *y, const double *Md, const uint64_t *x, si
   if (!gemv_win_on(lvl) || !gemv_fold_fits(Md, lvl, rk))
     return false;
   const FoldEntry &f = gemv_fold(Md, lvl, rk);
-  FoldUse use(f);
+  FoldUse use(f.K);
   k_gemv_batch(y, x, count, lvl, f.K, f.d.data(), (unsigned)f.d.size(), 1);
   return true;
 }
@@ -3582,42 +3576,10 @@ static bool rot_batch_fast(uint64_t *out, const uint64_t *x, size_t count, unsig
 {
   if (!gemv_win_on(lvl))
     return false;
-  const FoldEntry &f = rot_fold(r, lvl, rk);
-  FoldUse use(f);
-  k_gemv_batch(out, x, count, lvl, f.K, f.d.data(), 1, 0);
+  const RotFold &f = rotkey_fold(r, lvl, rk);
+  FoldUse use(f.K);
+  k_gemv_batch(out, x, count, lvl, f.K, &f.rot, 1, 0);
   return true;
-}
-
-// The key of rotation r folded for level lvl (he_gemv_bsgs_batch).  Entries
-// of an older key generation never match and are released at the next miss;
-// the least recently used go while the cache would exceed its cap.
-static const RotFold &bsgs_rot_fold(unsigned r, unsigned lvl, const he_evk_t rk[])
-{
-  const he_evk_t *k = find_rot_key(rk, r, galois_of_rot(r));
-  for (auto it = g_rfolds.begin(); it != g_rfolds.end(); ++it)
-    if (it->rot == r && it->lvl == lvl && it->gen == g_key_gen && it->rk == rk) {
-      g_rfolds.splice(g_rfolds.begin(), g_rfolds, it);
-      return g_rfolds.front();
-    }
-  const size_t bytes = k_gemv_fold_words(1, lvl) * 8;
-  for (auto it = g_rfolds.begin(); it != g_rfolds.end();)
-    if (it->gen != g_key_gen) {  // folded with keys that changed since
-      pool_free(it->K);
-      g_rfold_bytes -= it->bytes;
-      it = g_rfolds.erase(it);
-    } else {
-      ++it;
-    }
-  while (!g_rfolds.empty() && g_rfold_bytes + bytes > fold_cap()) {
-    pool_free(g_rfolds.back().K);
-    g_rfold_bytes -= g_rfolds.back().bytes;
-    g_rfolds.pop_back();
-  }
-  const GemvDiagIn dg{r, nullptr, k->data};
-  double *K = k_gemv_fold(&dg, 1, lvl);  // (an out-of-memory retry inside may empty the list)
-  g_rfolds.push_front(RotFold{rk, g_key_gen, lvl, r, K, bytes});
-  g_rfold_bytes += bytes;
-  return g_rfolds.front();
 }
 
 // A ciphertext of a batch as an object view (no payload of its own).
@@ -3694,8 +3656,8 @@ static void win_rot_chunk(uint64_t *out, const uint64_t *x, size_t x_stride, con
 {
   const size_t sw = (size_t)cnt * 2 * lvl * G.n;
   for (unsigned t = 0; t < nrot; t++) {
-    const RotFold &f = bsgs_rot_fold(rot[t], lvl, rk);
-    RotFoldUse use(f);
+    const RotFold &f = rotkey_fold(rot[t], lvl, rk);
+    FoldUse use(f.K);
     k_gemv_batch(out + t * sw, x + t * x_stride, cnt, lvl, f.K, &f.rot, 1, 0);
   }
 }
@@ -3720,20 +3682,91 @@ static void bsgs_baby_chunk(uint64_t *B, const uint64_t *x, unsigned cnt, unsign
   }
 }
 
+// The end of a chunk of the row-folded forms: the fold steps at level lvl - 1
+// -- y (cnt ciphertexts) rotated into R, then accumulated -- and the step's
+// tail y = uhat - y: the last fold step's kernel, or k_step_tail_batch where
+// there is no fold.
+static void fold_tail_chunk(uint64_t *y, uint64_t *R, const StepIn *st, const std::vector<unsigned> &fold,
+                            unsigned cnt, unsigned lvl, const he_evk_t rk[])
+{
+  const size_t ow = 2 * (size_t)(lvl - 1) * G.n;
+  for (size_t t = 0; t < fold.size(); t++) {
+    if (gemv_win_on(lvl - 1)) {
+      win_rot_chunk(R, y, 0, &fold[t], 1, cnt, lvl - 1, rk);
+    } else {
+      for (unsigned c = 0; c < cnt; c++) {
+        he_ct_t cx = ct_view(y + c * ow, lvl - 1), co = ct_view(R + c * ow, lvl - 1);
+        he_rot(&co, &cx, fold[t], rk);
+      }
+    }
+    if (st && t + 1 == fold.size())
+      k_rows_fold_tail_batch(y, R, st->uhat, lvl, cnt);
+    else
+      k_rows_fold_add_batch(y, R, lvl - 1, cnt);
+  }
+  if (st && fold.empty())
+    k_step_tail_batch(y, st->uhat, lvl, cnt);
+}
+
+// The entry check of every batch product: the context, the level, and y
+// (count ciphertexts at level lvl - 1) apart from every input (at level lvl).
+static void batch_check(const char *who, const uint64_t *y, const uint64_t *xa, const uint64_t *xb, const StepIn *st,
+                        size_t count, unsigned lvl)
+{
+  check_ctx();
+  if (lvl < 2 || lvl > G.L)
+    gpqhe_die("%s: bad level %u", who, lvl);
+  const size_t in_words = 2 * (size_t)lvl * G.n, out_words = 2 * (size_t)(lvl - 1) * G.n;
+  const uint64_t *ins[4] = {st ? st->xhat : xa, st ? st->xr : xb, st ? st->uhat : nullptr, st ? st->ur : nullptr};
+  for (const uint64_t *x : ins)
+    if (x && y < x + count * in_words && x < y + count * out_words)
+      gpqhe_die("%s: output overlaps %s input", who, ins[1] ? "an" : "the");
+}
+
+// Ciphertexts per chunk: as many as GPQHE_WS_MIB holds at per_ct_words each,
+// at most cap, in equal chunks (a short last one runs at a fraction of the
+// GPU's width).  hook: the test variable that forces several chunks on a small
+// batch.  The two hooks differ, and are kept as they are: GPQHE_BSGS_CHUNK is
+// the chunk as given, GPQHE_CHUNK (the I/O calls') is equalised like any other.
+static size_t batch_chunk_size(size_t count, size_t per_ct_words, size_t cap, const char *hook)
+{
+  size_t chunk = std::min(std::max<size_t>(1, bsgs_budget() / per_ct_words), std::max<size_t>(1, cap));
+  if (const char *e = getenv(hook)) {
+    chunk = std::max<size_t>(1, std::min<size_t>(chunk, strtoul(e, nullptr, 0)));
+    if (!strcmp(hook, "GPQHE_BSGS_CHUNK"))
+      return chunk;
+  }
+  const size_t nchunks = (count + chunk - 1) / chunk;
+  return (count + nchunks - 1) / nchunks;
+}
+
+// The chunk loop of a batch product at level lvl: run(y, xa, xb, st, cnt) on
+// each chunk's part of y and of the operands (st null) or of the step's inputs.
+template <class Run>
+static void batch_chunks(uint64_t *y, const uint64_t *xa, const uint64_t *xb, const StepIn *st, size_t count,
+                         unsigned lvl, size_t chunk, Run run)
+{
+  const size_t in_words = 2 * (size_t)lvl * G.n, out_words = 2 * (size_t)(lvl - 1) * G.n;
+  for (size_t c0 = 0; c0 < count; c0 += chunk) {
+    const unsigned cnt = (unsigned)std::min(chunk, count - c0);
+    const size_t o = c0 * in_words;
+    const StepIn sc = st ? StepIn{st->xhat + o, st->xr + o, st->uhat + o, st->ur + o} : StepIn{};
+    run(y + c0 * out_words, st ? nullptr : xa + o, st || !xb ? nullptr : xb + o, st ? &sc : nullptr, cnt);
+  }
+}
+
 // One chunk of cnt ciphertexts, y = Ma xa + Mb xb: ka / kb the baby rotations
 // of each operand (kb empty: the single product), kg the giant steps of the
 // union, fold the rotate-and-add steps at level lvl - 1 behind the rescale.
 // st: form xa = xhat - xr and xb = uhat - ur first (into slot 0 of the
 // operand's baby slots where its plan uses the unrotated slot, else into a
-// workspace) and finish with y = uhat - y: the last fold step's kernel, or
-// k_step_tail_batch where there is no fold.
+// workspace) and finish with y = uhat - y (fold_tail_chunk).
 static void bsgs_chunk(uint64_t *y, const uint64_t *xa, const uint64_t *xb, const StepIn *st, unsigned cnt,
                        unsigned lvl, const BsgsPlan &plan, const BsgsKeys &ka, const BsgsKeys &kb, const BsgsKeys &kg,
                        const std::vector<unsigned> &fold, const he_evk_t rk[], size_t budget)
 {
   const unsigned nm = lvl + G.K, ndig = (lvl + G.alpha - 1) / G.alpha;
   const size_t n = G.n, pw = (size_t)lvl * n, cw = 2 * pw, sw = (size_t)cnt * cw;  // words: ciphertext, slot
-  const size_t ow = 2 * (size_t)(lvl - 1) * n;                                     // ... of y
   const unsigned nbs = ka.nbs + kb.nbs;
   // (the rotated giant steps, then the fold's rotated copy, take the baby
   // slots' place: the inner sums are the last to read those)
@@ -3774,23 +3807,7 @@ static void bsgs_chunk(uint64_t *y, const uint64_t *xa, const uint64_t *xb, cons
   }
   k_moddown(y, (size_t)(lvl - 1) * n, S, pw, 2 * cnt, lvl, 2);
 
-  // the fold at level lvl - 1: the whole chunk rotated into R, then accumulated
-  for (size_t t = 0; t < fold.size(); t++) {
-    if (gemv_win_on(lvl - 1)) {
-      win_rot_chunk(R, y, 0, &fold[t], 1, cnt, lvl - 1, rk);
-    } else {
-      for (unsigned c = 0; c < cnt; c++) {
-        he_ct_t cx = ct_view(y + c * ow, lvl - 1), co = ct_view(R + c * ow, lvl - 1);
-        he_rot(&co, &cx, fold[t], rk);
-      }
-    }
-    if (st && t + 1 == fold.size())
-      k_rows_fold_tail_batch(y, R, st->uhat, lvl, cnt);
-    else
-      k_rows_fold_add_batch(y, R, lvl - 1, cnt);
-  }
-  if (st && fold.empty())
-    k_step_tail_batch(y, st->uhat, lvl, cnt);
+  fold_tail_chunk(y, R, st, fold, cnt, lvl, rk);
 }
 
 // What an entry point's own argument checks leave for the run: the rotation
@@ -3801,24 +3818,17 @@ struct BatchKind {
 };
 
 // The run of every entry point: check() makes the entry point's own argument
-// checks (after the level's), get(hold) looks its plan up.  Plan, then keys,
+// checks (after batch_check's), get(hold) looks its plan up.  Plan, then keys,
 // then the first launch.
 template <class Check, class Get>
 static void bsgs_run(const char *who, uint64_t *y, const uint64_t *xa, const uint64_t *xb, const StepIn *st,
                      size_t count, unsigned lvl, const he_evk_t rk[], Check check, Get get)
 {
-  check_ctx();
-  if (lvl < 2 || lvl > G.L)
-    gpqhe_die("%s: bad level %u", who, lvl);
+  batch_check(who, y, xa, xb, st, count, lvl);
   const BatchKind kind = check();
-  const unsigned nm = lvl + G.K, ndig = (lvl + G.alpha - 1) / G.alpha;
-  const size_t n = G.n, pw = (size_t)lvl * n, in_words = 2 * pw, out_words = 2 * (size_t)(lvl - 1) * n;
+  const size_t pw = (size_t)lvl * G.n, in_words = 2 * pw, out_words = 2 * (size_t)(lvl - 1) * G.n;
   if (!count)
     return;
-  const uint64_t *ins[4] = {st ? st->xhat : xa, st ? st->xr : xb, st ? st->uhat : nullptr, st ? st->ur : nullptr};
-  for (const uint64_t *x : ins)
-    if (x && y < x + count * in_words && x < y + count * out_words)
-      gpqhe_die("%s: output overlaps %s input", who, ins[1] ? "an" : "the");
 
   PlanHold hold;
   const BsgsPlan *plan = get(hold);
@@ -3844,23 +3854,13 @@ static void bsgs_run(const char *who, uint64_t *y, const uint64_t *xa, const uin
   //   + 1 per operand of a step whose difference has no slot 0 to live in;
   // on the windowed path k_gemv_batch's workspace besides (the generic stages'
   // workspaces do not grow with the chunk)
-  const size_t budget = bsgs_budget();
   const size_t slots_ct =
     std::max(ka.nbs + kb.nbs, kg.njr) + kg.nj + (kg.njr ? 1 : 0) + (st ? !ka.has0 + !kb.has0 : 0);
-  const size_t per_ct =
-    slots_ct * 2 * pw + (gemv_win_on(lvl) ? ((size_t)lvl + (size_t)ndig * nm + 2 * (size_t)nm) * n : 0);
-  size_t chunk = std::min<size_t>(std::max<size_t>(1, budget / per_ct), 16384);
-  if (const char *e = getenv("GPQHE_BSGS_CHUNK"))  // test hook: several chunks on a small batch
-    chunk = std::max<size_t>(1, std::min<size_t>(chunk, strtoul(e, nullptr, 0)));
-  else  // equal chunks: a short last one runs at a fraction of the GPU's width
-    chunk = (count + (count + chunk - 1) / chunk - 1) / ((count + chunk - 1) / chunk);
-  for (size_t c0 = 0; c0 < count; c0 += chunk) {
-    const unsigned cnt = (unsigned)std::min(chunk, count - c0);
-    const size_t o = c0 * in_words;
-    const StepIn sc = st ? StepIn{st->xhat + o, st->xr + o, st->uhat + o, st->ur + o} : StepIn{};
-    bsgs_chunk(y + c0 * out_words, st ? nullptr : xa + o, st || !xb ? nullptr : xb + o, st ? &sc : nullptr, cnt, lvl,
-               *plan, ka, kb, kg, kind.fold, rk, budget);
-  }
+  const size_t per_ct = slots_ct * 2 * pw + (gemv_win_on(lvl) ? k_gemv_batch_ws_words(lvl) : 0);
+  batch_chunks(y, xa, xb, st, count, lvl, batch_chunk_size(count, per_ct, 16384, "GPQHE_BSGS_CHUNK"),
+               [&](uint64_t *yc, const uint64_t *xac, const uint64_t *xbc, const StepIn *sc, unsigned cnt) {
+                 bsgs_chunk(yc, xac, xbc, sc, cnt, lvl, *plan, ka, kb, kg, kind.fold, rk, bsgs_budget());
+               });
 }
 
 // g = 0: the default; g > slots: an error (the check() of the forms with giant steps)
@@ -4031,20 +4031,30 @@ static const BsgsPlan *rows_plan_get(PlanHold &h, const double *Ma, const double
     });
 }
 
-// sl: the slots of one loop; it divides the context's (a power of two)
-static void rows_check_loops(const char *who, unsigned sl)
+// The loops of a packed call: P = slots / s; dies unless s, the slots of one
+// loop, is a power of two dividing the context's.
+static unsigned packed_loops(const char *who, unsigned s)
 {
-  if (!sl || (sl & (sl - 1)) || sl > G.slots)
-    gpqhe_die("%s: s = %u, slots = %u", who, sl, G.slots);
+  if (!s || (s & (s - 1)) || s > G.slots)
+    gpqhe_die("%s: s = %u, slots = %u", who, s, G.slots);
+  return G.slots / s;
+}
+
+// ... and of a row-folded one: rows of the s, one matrix or one per loop.
+static unsigned rows_loops(const char *who, unsigned s, unsigned rows, unsigned nmat)
+{
+  const unsigned P = packed_loops(who, s);
+  if (!rows || rows > s)
+    gpqhe_die("%s: rows = %u, s = %u", who, rows, s);
+  if (nmat != 1 && nmat != P)
+    gpqhe_die("%s: %u matrices for %u loops", who, nmat, P);
+  return P;
 }
 
 static void rows_genrk(const char *who, he_evk_t rk[], const poly_mpi_t *sk, unsigned sl, unsigned rows)
 {
   check_ctx();
-  rows_check_loops(who, sl);
-  if (!rows || rows > sl)
-    gpqhe_die("%s: rows = %u, slots = %u", who, rows, sl);
-  const unsigned mp = rows_pow2(rows), P = G.slots / sl;
+  const unsigned P = rows_loops(who, sl, rows, 1), mp = rows_pow2(rows);
   gen_rot_keys(rk, sk, [=](unsigned r) {
     const unsigned i = r / P;                                   // the loops' own rotation (r = i P)
     const bool fold = i % mp == 0 && !(i / mp & (i / mp - 1));  // m' 2^t
@@ -4070,12 +4080,7 @@ static void rows_run(const char *who, uint64_t *y, const double *Ma, const doubl
   bsgs_run(
     who, y, xa, xb, st, count, lvl, rk,
     [&] {
-      rows_check_loops(who, sl);
-      const unsigned P = G.slots / sl;
-      if (!rows || rows > sl)
-        gpqhe_die("%s: rows = %u, slots = %u", who, rows, sl);
-      if (nmat != 1 && nmat != P)
-        gpqhe_die("%s: %u matrices for %u loops", who, nmat, P);
+      const unsigned P = rows_loops(who, sl, rows, nmat);
       BatchKind kind{1, {}};  // the fold: the rotations m' P, 2 m' P, .. < S
       for (unsigned r = rows_pow2(rows); r < sl; r <<= 1)
         kind.fold.push_back(r * P);
@@ -4136,11 +4141,7 @@ static size_t ntt_group_polys(unsigned nlimbs);
 
 static size_t io_chunk(size_t count, size_t per_ct_words, size_t cap)
 {
-  size_t chunk = std::min(std::max<size_t>(1, bsgs_budget() / per_ct_words), std::max<size_t>(1, cap));
-  if (const char *e = getenv("GPQHE_CHUNK"))
-    chunk = std::max<size_t>(1, std::min<size_t>(chunk, strtoul(e, nullptr, 0)));
-  const size_t nchunks = (count + chunk - 1) / chunk;  // equal chunks, as the other batch calls
-  return (count + nchunks - 1) / nchunks;
+  return batch_chunk_size(count, per_ct_words, cap, "GPQHE_CHUNK");
 }
 
 // k_ntt over npolys polynomials of nlimbs limbs in poly_ntt_batch's groups
@@ -4236,15 +4237,6 @@ extern "C" void he_enc_pk_batch(uint64_t *x, const gpqhe_complex_t z[], size_t c
   enc_pk_run("he_enc_pk_batch", x, z, count, slots, scale, nlimbs, pk, 0, 0);
 }
 
-// The loops of a packed call: P = slots / s; dies unless s is a power of two
-// dividing the context's slots.
-static unsigned packed_loops(const char *who, unsigned s)
-{
-  if (!s || (s & (s - 1)) || s > G.slots)
-    gpqhe_die("%s: s = %u, slots = %u", who, s, G.slots);
-  return G.slots / s;
-}
-
 extern "C" void he_enc_pk_packed_batch(uint64_t *x, const gpqhe_complex_t z[], size_t count, unsigned int s,
                                        unsigned int width, double scale, unsigned int nlimbs, const he_pk_t *pk)
 {
@@ -4335,9 +4327,7 @@ extern "C" void he_dec_dcd_packed_batch(gpqhe_complex_t z[], const uint64_t *y, 
 {
   HPROF("dec_dcd_packed_batch");
   check_ctx();
-  const unsigned P = packed_loops("he_dec_dcd_packed_batch", s);
-  if (!rows || rows > s)
-    gpqhe_die("he_dec_dcd_packed_batch: rows = %u, s = %u", rows, s);
+  const unsigned P = rows_loops("he_dec_dcd_packed_batch", s, rows, 1);
   // (one loop read whole: z is the decoded vector)
   dec_dcd_run("he_dec_dcd_packed_batch", z, y, count, nlimbs, scale, G.slots, sk, P == 1 && rows == s ? 0 : P, rows);
 }
@@ -4359,11 +4349,7 @@ extern "C" void he_enc_gain_packed_batch(uint64_t *D, const gpqhe_complex_t M[],
   HPROF("enc_gain_packed_batch");
   const char *who = "he_enc_gain_packed_batch";
   check_ctx();
-  const unsigned P = packed_loops(who, s);
-  if (!rows || rows > s)
-    gpqhe_die("%s: rows = %u, s = %u", who, rows, s);
-  if (nmat != 1 && nmat != P)
-    gpqhe_die("%s: %u matrices for %u loops", who, nmat, P);
+  rows_loops(who, s, rows, nmat);
   io_check(who, nlimbs, G.slots);
   if (!M)
     gpqhe_die("%s: null argument", who);
@@ -4386,7 +4372,6 @@ static void encgain_chunk(uint64_t *y, const uint64_t *DA, const uint64_t *DB, c
                           const std::vector<unsigned> &fold, const he_evk_t rk[], const he_evk_t *rlk, size_t budget)
 {
   const size_t n = G.n, pw = (size_t)lvl * n, cw = 2 * pw, sw = (size_t)cnt * cw;
-  const size_t ow = 2 * (size_t)(lvl - 1) * n;
   Ws W((2 * (size_t)(mp - 1) + 3 + (st ? 2 : 0)) * sw);
   uint64_t *Ra = W.p, *Rb = Ra + (mp - 1) * sw, *X01 = Rb + (mp - 1) * sw, *Q = X01 + sw, *one = Q + sw;
   if (st) {
@@ -4406,23 +4391,7 @@ static void encgain_chunk(uint64_t *y, const uint64_t *DA, const uint64_t *DB, c
   uint64_t *quad = X01, *R = one;
   mul_chunk(quad, (size_t)(lvl - 1) * n, Q, one, cw, pw, cnt, lvl, rlk, true);
   k_rows_fold_add_batch(y, quad, lvl - 1, cnt);
-  // the fold at level lvl - 1 and the step's tail, as bsgs_chunk's
-  for (size_t t = 0; t < fold.size(); t++) {
-    if (gemv_win_on(lvl - 1)) {
-      win_rot_chunk(R, y, 0, &fold[t], 1, cnt, lvl - 1, rk);
-    } else {
-      for (unsigned c = 0; c < cnt; c++) {
-        he_ct_t cx = ct_view(y + c * ow, lvl - 1), co = ct_view(R + c * ow, lvl - 1);
-        he_rot(&co, &cx, fold[t], rk);
-      }
-    }
-    if (st && t + 1 == fold.size())
-      k_rows_fold_tail_batch(y, R, st->uhat, lvl, cnt);
-    else
-      k_rows_fold_add_batch(y, R, lvl - 1, cnt);
-  }
-  if (st && fold.empty())
-    k_step_tail_batch(y, st->uhat, lvl, cnt);
+  fold_tail_chunk(y, R, st, fold, cnt, lvl, rk);
 }
 
 // The run of both cloud-side entry points: argument checks, then keys, then
@@ -4431,24 +4400,16 @@ static void encgain_run(const char *who, uint64_t *y, const uint64_t *DA, const 
                         const uint64_t *xb, const StepIn *st, size_t count, unsigned lvl, const he_evk_t rk[],
                         const he_evk_t *rlk, unsigned sl, unsigned rows)
 {
-  check_ctx();
-  if (lvl < 2 || lvl > G.L)
-    gpqhe_die("%s: bad level %u", who, lvl);
-  const unsigned P = packed_loops(who, sl);
-  if (!rows || rows > sl)
-    gpqhe_die("%s: rows = %u, slots = %u", who, rows, sl);
+  batch_check(who, y, xa, xb, st, count, lvl);
+  const unsigned P = rows_loops(who, sl, rows, 1);
   if (!rlk || !rlk->data || rlk->dnum != G.dnum)
     gpqhe_die("%s: relinearization key missing or built for another dnum", who);
   const unsigned mp = rows_pow2(rows), nm = lvl + G.K, ndig = (lvl + G.alpha - 1) / G.alpha;
-  const size_t n = G.n, pw = (size_t)lvl * n, in_words = 2 * pw, out_words = 2 * (size_t)(lvl - 1) * n;
+  const size_t pw = (size_t)lvl * G.n, in_words = 2 * pw, out_words = 2 * (size_t)(lvl - 1) * G.n;
   if (!count)
     return;
   if (!y || !DA || !DB)
     gpqhe_die("%s: null argument", who);
-  const uint64_t *ins[4] = {st ? st->xhat : xa, st ? st->xr : xb, st ? st->uhat : nullptr, st ? st->ur : nullptr};
-  for (const uint64_t *x : ins)
-    if (x && y < x + count * in_words && x < y + count * out_words)
-      gpqhe_die("%s: output overlaps an input", who);
   for (const uint64_t *d : {DA, DB})
     if (y < d + mp * in_words && d < y + count * out_words)
       gpqhe_die("%s: output overlaps a diagonal", who);
@@ -4466,24 +4427,18 @@ static void encgain_run(const char *who, uint64_t *y, const uint64_t *DA, const 
   // a ciphertext's share of a chunk: the slots of encgain_chunk, and the larger
   // of the multiply's workspace (he_mul_rescale_batch's count) and, on the
   // windowed path, k_gemv_batch's
-  const size_t budget = bsgs_budget();
-  const size_t mul_ws = k_mul_split_ok(lvl) ? (size_t)lvl + (size_t)ndig * nm + 2 * (G.K + 1) + 2 * (size_t)lvl
-                                            : 6 * (size_t)lvl + (size_t)ndig * nm + 2 * (size_t)nm;
-  const size_t rot_ws = gemv_win_on(lvl) ? (size_t)lvl + (size_t)ndig * nm + 2 * (size_t)nm : 0;
-  const size_t per_ct = (2 * (size_t)(mp - 1) + 3 + (st ? 2 : 0)) * 2 * pw + std::max(mul_ws, rot_ws) * n;
-  size_t chunk = std::min<size_t>(std::max<size_t>(1, budget / per_ct), 16384);
-  chunk = std::min<size_t>(chunk, 65535 / (ndig * nm));  // (the multiply's launch grid)
-  if (const char *e = getenv("GPQHE_BSGS_CHUNK"))  // test hook: several chunks on a small batch
-    chunk = std::max<size_t>(1, std::min<size_t>(chunk, strtoul(e, nullptr, 0)));
-  else  // equal chunks: a short last one runs at a fraction of the GPU's width
-    chunk = (count + (count + chunk - 1) / chunk - 1) / ((count + chunk - 1) / chunk);
-  for (size_t c0 = 0; c0 < count; c0 += chunk) {
-    const unsigned cnt = (unsigned)std::min(chunk, count - c0);
-    const size_t o = c0 * in_words;
-    const StepIn sc = st ? StepIn{st->xhat + o, st->xr + o, st->uhat + o, st->ur + o} : StepIn{};
-    encgain_chunk(y + c0 * out_words, DA, DB, st ? nullptr : xa + o, st ? nullptr : xb + o, st ? &sc : nullptr, cnt,
-                  lvl, mp, kb, fold, rk, rlk, budget);
-  }
+  const size_t mul_ws = (k_mul_split_ok(lvl) ? (size_t)lvl + (size_t)ndig * nm + 2 * (G.K + 1) + 2 * (size_t)lvl
+                                             : 6 * (size_t)lvl + (size_t)ndig * nm + 2 * (size_t)nm)
+                        << G.logn;
+  const size_t rot_ws = gemv_win_on(lvl) ? k_gemv_batch_ws_words(lvl) : 0;
+  const size_t per_ct = (2 * (size_t)(mp - 1) + 3 + (st ? 2 : 0)) * 2 * pw + std::max(mul_ws, rot_ws);
+  // (65535: the multiply's launch grid)
+  const size_t cap = std::min<size_t>(16384, 65535 / (ndig * nm));
+  const size_t chunk = batch_chunk_size(count, per_ct, cap, "GPQHE_BSGS_CHUNK");
+  batch_chunks(y, xa, xb, st, count, lvl, chunk,
+               [&](uint64_t *yc, const uint64_t *xac, const uint64_t *xbc, const StepIn *sc, unsigned cnt) {
+                 encgain_chunk(yc, DA, DB, xac, xbc, sc, cnt, lvl, mp, kb, fold, rk, rlk, bsgs_budget());
+               });
 }
 
 extern "C" void he_gemv2_encgain_packed_batch(uint64_t *y, const uint64_t *DA, const uint64_t *xa, const uint64_t *DB,

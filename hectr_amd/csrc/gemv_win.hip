@@ -838,6 +838,14 @@ size_t k_gemv_fold_words(unsigned E, unsigned lvl)
   return gw_kbase(nm, ndig, E, G.logn) + ((size_t)lvl * E << G.logn);
 }
 
+// k_gemv_batch's workspace per ciphertext: the rescaled input's limbs, the
+// ModUp digits and the accumulator pair.
+size_t k_gemv_batch_ws_words(unsigned lvl)
+{
+  const unsigned ndig = (lvl + G.alpha - 1) / G.alpha, nm = lvl + G.K;
+  return ((size_t)lvl + (size_t)ndig * nm + 2 * (size_t)nm) << G.logn;
+}
+
 double *k_gemv_fold(const GemvDiagIn *dg, unsigned E, unsigned lvl)
 {
   const unsigned ndig = (lvl + G.alpha - 1) / G.alpha, nm = lvl + G.K;
@@ -873,7 +881,7 @@ static void gemv_chunk(uint64_t *y, size_t y_stride, size_t y_pstride, const uin
   std::vector<int> yi((size_t)nm * 3, -1);
   const size_t ys = (size_t)lvl * n, as = 2 * (size_t)nm * n;
   size_t ds = (size_t)ndig * nm * n;
-  uint64_t *ws = (uint64_t *)pool_alloc((size_t)cnt * (ys + ds + as) * 8);
+  uint64_t *ws = (uint64_t *)pool_alloc((size_t)cnt * k_gemv_batch_ws_words(lvl) * 8);
   uint64_t *ybuf = ws, *Dc = ybuf + cnt * ys, *acc = Dc + cnt * ds;
   if (k_modup_c1_split(Dc, ybuf, x, x_stride, x_pstride, cnt, lvl)) {
     for (unsigned j = 0; j < ndig; j++)

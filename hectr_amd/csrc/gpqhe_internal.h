@@ -512,6 +512,7 @@ struct GemvDiagIn {
 // doubles (pool memory; the caller caches and frees it)
 double *k_gemv_fold(const GemvDiagIn *dg, unsigned E, unsigned lvl);
 size_t k_gemv_fold_words(unsigned E, unsigned lvl);
+size_t k_gemv_batch_ws_words(unsigned lvl);  // k_gemv_batch's workspace, per ciphertext
 // y [count][2][keep][n] = ModDown(sum over the folded diagonals d[e] of the
 // rotated key switch of x [count][2][lvl][n]); mode 1: by P q_{lvl-1} (he_gemv,
 // keep = lvl - 1), 0: by P (he_rot, keep = lvl)

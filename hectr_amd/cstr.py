@@ -428,60 +428,44 @@ class EncryptedRegulator:
         e.free_evks(self.rk)
 
 
-class BatchedEncryptedRegulator:
-    """ctr_hempc for `count` control loops at once through the three batch
-    calls: one he_enc_pk_batch of the 4 count vectors (into one device array
-    sliced four ways), he_hempc_step_batch, he_dec_dcd_batch.  The loops share
-    the problem's gain matrices, the key pair and the he_genrk_bsgs(g) rotation
-    keys.  With rows=k (k >= nu: only the first nu entries of the result are
-    used) the step is he_hempc_step_rows_batch, the row-folded product of the k
-    leading rows, on the he_genrk_rows(k) keys.  Device memory comes from torch."""
+class _BatchRegulator:
+    """What the batch regulators share: context and keys, the device arrays (x:
+    the 4 count input ciphertexts of one encrypt call, sliced four ways; up:
+    the count results; from torch), and the step -- pack, encrypt, step,
+    decode, check, time.  A subclass supplies _genrk, _enc, _step and _dcd."""
 
-    def __init__(self, engine, problem: CstrProblem, count, g=0, seed=None, logn=12, logq=109, log_delta=50,
-                 init=True, rows=None):
+    def _setup(self, engine, slots, count, zshape, nu, seed, logn, logq, log_delta, init):
+        """zshape: (vectors given, vectors encoded, their width) per input."""
         import torch
-        self.e, self.pb, self.count, self.g, self.rows = engine, problem, count, g, rows
-        assert rows is None or problem.nu <= rows <= problem.slots
+        self.e, self.count, self._zshape, self._nu = engine, count, zshape, nu
         if init:
-            engine.init(logn, logq, problem.slots, log_delta)
+            engine.init(logn, logq, slots, log_delta)
         if seed is not None:
             engine.set_seed(seed)
-        s = problem.slots
         self.pk, self.sk = engine.pk(), engine.sk()
-        self.rk = engine.evks(s)
+        self.rk = engine.evks(slots)
         engine.keypair(self.pk, self.sk)
-        if rows is None:
-            engine.genrk_bsgs(self.rk, self.sk, g)
-        else:
-            engine.genrk_rows(self.rk, self.sk, rows)
+        self._genrk()
         self.lvl, self.scale = engine.L, engine.info.delta
         self.cw = 2 * self.lvl * engine.n                  # words of one input ciphertext
         self.x = torch.zeros(4 * count * self.cw, dtype=torch.int64, device="cuda")
         self.up = torch.zeros(count * 2 * (self.lvl - 1) * engine.n, dtype=torch.int64, device="cuda")
         torch.cuda.synchronize()
-        self.MAz = d2z_matrix(problem.MA, s).ravel()
-        self.MBz = d2z_matrix(problem.MB, s).ravel()
         self.timings = []
 
     def __call__(self, xhat, uhat, xr, ur):
-        e, s, cnt = self.e, self.pb.slots, self.count
+        given, rows, width = self._zshape
         t0 = time.perf_counter()
-        zs = np.zeros((4, cnt, s), dtype=np.complex128)
+        zs = np.zeros((4, rows, width), dtype=np.complex128)
         for b, v in enumerate((xhat, xr, uhat, ur)):
-            v = np.asarray(v, dtype=np.float64).reshape(cnt, -1)
-            zs[b, :, :v.shape[1]] = v
-        e.enc_pk_batch(self.x.data_ptr(), zs.reshape(4 * cnt, s), self.pk, s, self.scale, self.lvl)
-        part = [self.x.data_ptr() + 8 * b * cnt * self.cw for b in range(4)]
-        if self.rows is None:
-            e.hempc_step_batch(self.up.data_ptr(), self.MAz, self.MBz, part[0], part[1], part[2], part[3], cnt,
-                               self.lvl, self.rk, self.g)
-        else:
-            e.hempc_step_rows_batch(self.up.data_ptr(), self.MAz, self.MBz, part[0], part[1], part[2], part[3], cnt,
-                                    self.lvl, self.rk, self.rows)
-        uz = e.dec_dcd_batch(self.up.data_ptr(), cnt, self.lvl - 1, self.scale, self.sk, s)
+            v = np.asarray(v, dtype=np.float64).reshape(given, -1)
+            zs[b, :given, :v.shape[1]] = v
+        self._enc(zs)
+        self._step(*(self.x.data_ptr() + 8 * b * self.count * self.cw for b in range(4)))
+        uz = self._dcd()                                   # [vectors encoded][.]
         assert np.all(uz.imag < HECTR_SMALL), "imaginary part too large (src/ctr.c:493-494)"
         self.timings.append(time.perf_counter() - t0)
-        return uz.real[:, :self.pb.nu].copy()
+        return uz.real[:given, :self._nu].copy()
 
     def close(self):
         e = self.e
@@ -492,7 +476,47 @@ class BatchedEncryptedRegulator:
         self.x = self.up = None
 
 
-class PackedEncryptedRegulator:
+class BatchedEncryptedRegulator(_BatchRegulator):
+    """ctr_hempc for `count` control loops at once through the three batch
+    calls: one he_enc_pk_batch of the 4 count vectors (into one device array
+    sliced four ways), he_hempc_step_batch, he_dec_dcd_batch.  The loops share
+    the problem's gain matrices, the key pair and the he_genrk_bsgs(g) rotation
+    keys.  With rows=k (k >= nu: only the first nu entries of the result are
+    used) the step is he_hempc_step_rows_batch, the row-folded product of the k
+    leading rows, on the he_genrk_rows(k) keys.  Device memory comes from torch."""
+
+    def __init__(self, engine, problem: CstrProblem, count, g=0, seed=None, logn=12, logq=109, log_delta=50,
+                 init=True, rows=None):
+        self.pb, self.g, self.rows = problem, g, rows
+        assert rows is None or problem.nu <= rows <= problem.slots
+        s = problem.slots
+        self._setup(engine, s, count, (count, count, s), problem.nu, seed, logn, logq, log_delta, init)
+        self.MAz = d2z_matrix(problem.MA, s).ravel()
+        self.MBz = d2z_matrix(problem.MB, s).ravel()
+
+    def _genrk(self):
+        if self.rows is None:
+            self.e.genrk_bsgs(self.rk, self.sk, self.g)
+        else:
+            self.e.genrk_rows(self.rk, self.sk, self.rows)
+
+    def _enc(self, zs):
+        s = self.pb.slots
+        self.e.enc_pk_batch(self.x.data_ptr(), zs.reshape(4 * self.count, s), self.pk, s, self.scale, self.lvl)
+
+    def _step(self, xhat, xr, uhat, ur):
+        e, up = self.e, self.up.data_ptr()
+        if self.rows is None:
+            e.hempc_step_batch(up, self.MAz, self.MBz, xhat, xr, uhat, ur, self.count, self.lvl, self.rk, self.g)
+        else:
+            e.hempc_step_rows_batch(up, self.MAz, self.MBz, xhat, xr, uhat, ur, self.count, self.lvl, self.rk,
+                                    self.rows)
+
+    def _dcd(self):
+        return self.e.dec_dcd_batch(self.up.data_ptr(), self.count, self.lvl - 1, self.scale, self.sk, self.pb.slots)
+
+
+class PackedEncryptedRegulator(_BatchRegulator):
     """ctr_hempc for many control loops per ciphertext (include/gpqhe_ext_packed_batch.h):
     a context of slots_total slots carries P = slots_total / s loops of s =
     problem.slots slots, entry k of loop p at slot k P + p, so len(problems)
@@ -507,31 +531,19 @@ class PackedEncryptedRegulator:
 
     def __init__(self, engine, problems, slots_total, rows=None, seed=None, logn=12, logq=109, log_delta=50,
                  init=True):
-        import torch
         pb = problems[0]
         s = pb.slots
-        self.e, self.problems, self.s, self.S = engine, list(problems), s, slots_total
+        self.problems, self.s, self.S = list(problems), s, slots_total
         self.rows = pb.nu if rows is None else rows
         assert all(q.slots == s and (q.nx, q.nu) == (pb.nx, pb.nu) for q in problems)
         assert slots_total % s == 0 and pb.nu <= self.rows <= s
         self.P = P = slots_total // s
         self.nloops = len(problems)
-        self.count = count = -(-self.nloops // P)
-        if init:
-            engine.init(logn, logq, slots_total, log_delta)
-        assert engine.slots == slots_total
-        if seed is not None:
-            engine.set_seed(seed)
-        self.pk, self.sk = engine.pk(), engine.sk()
-        self.rk = engine.evks(slots_total)
-        engine.keypair(self.pk, self.sk)
-        engine.genrk_packed(self.rk, self.sk, s, self.rows)
-        self.lvl, self.scale = engine.L, engine.info.delta
-        self.cw = 2 * self.lvl * engine.n                  # words of one input ciphertext
-        self.x = torch.zeros(4 * count * self.cw, dtype=torch.int64, device="cuda")
-        self.up = torch.zeros(count * 2 * (self.lvl - 1) * engine.n, dtype=torch.int64, device="cuda")
-        torch.cuda.synchronize()
+        count = -(-self.nloops // P)
         self.width = max(pb.nx, pb.nu)
+        self._setup(engine, slots_total, count, (self.nloops, count * P, self.width), pb.nu, seed, logn, logq,
+                    log_delta, init)
+        assert engine.slots == slots_total
         r = self.rows
         if all(q is pb for q in problems):
             self.nmat = 1
@@ -548,31 +560,22 @@ class PackedEncryptedRegulator:
             zero = np.zeros((r, s), dtype=np.complex128)
             self.MAz = np.stack([d2z_matrix(q.MA, s)[:r] if q else zero for q in owner]).ravel()
             self.MBz = np.stack([d2z_matrix(q.MB, s)[:r] if q else zero for q in owner]).ravel()
-        self.timings = []
 
-    def __call__(self, xhat, uhat, xr, ur):
-        e, cnt, P, w = self.e, self.count, self.P, self.width
-        t0 = time.perf_counter()
-        zs = np.zeros((4, cnt * P, w), dtype=np.complex128)
-        for b, v in enumerate((xhat, xr, uhat, ur)):
-            v = np.asarray(v, dtype=np.float64).reshape(self.nloops, -1)
-            zs[b, :self.nloops, :v.shape[1]] = v
-        e.enc_pk_packed_batch(self.x.data_ptr(), zs.reshape(4 * cnt, P, w), self.pk, self.s, w, self.scale, self.lvl)
-        part = [self.x.data_ptr() + 8 * b * cnt * self.cw for b in range(4)]
-        e.hempc_step_packed_batch(self.up.data_ptr(), self.MAz, self.MBz, part[0], part[1], part[2], part[3], cnt,
-                                  self.lvl, self.rk, self.s, self.rows, self.nmat)
-        uz = e.dec_dcd_packed_batch(self.up.data_ptr(), cnt, self.lvl - 1, self.scale, self.sk, self.s, self.rows)
-        assert np.all(uz.imag < HECTR_SMALL), "imaginary part too large (src/ctr.c:493-494)"
-        self.timings.append(time.perf_counter() - t0)
-        return uz.real.reshape(cnt * P, self.rows)[:self.nloops, :self.problems[0].nu].copy()
+    def _genrk(self):
+        self.e.genrk_packed(self.rk, self.sk, self.s, self.rows)
 
-    def close(self):
-        e = self.e
-        e.sync()
-        e.free(self.pk)
-        e.free(self.sk)
-        e.free_evks(self.rk)
-        self.x = self.up = None
+    def _enc(self, zs):
+        self.e.enc_pk_packed_batch(self.x.data_ptr(), zs.reshape(4 * self.count, self.P, self.width), self.pk, self.s,
+                                   self.width, self.scale, self.lvl)
+
+    def _step(self, xhat, xr, uhat, ur):
+        self.e.hempc_step_packed_batch(self.up.data_ptr(), self.MAz, self.MBz, xhat, xr, uhat, ur, self.count,
+                                       self.lvl, self.rk, self.s, self.rows, self.nmat)
+
+    def _dcd(self):
+        uz = self.e.dec_dcd_packed_batch(self.up.data_ptr(), self.count, self.lvl - 1, self.scale, self.sk, self.s,
+                                         self.rows)
+        return uz.reshape(self.count * self.P, self.rows)
 
 
 class EncryptedGainRegulator(PackedEncryptedRegulator):
@@ -599,21 +602,9 @@ class EncryptedGainRegulator(PackedEncryptedRegulator):
         engine.enc_gain_packed_batch(self.DA, self.MAz, self.pk, self.s, self.rows, self.lvl, self.nmat)
         engine.enc_gain_packed_batch(self.DB, self.MBz, self.pk, self.s, self.rows, self.lvl, self.nmat)
 
-    def __call__(self, xhat, uhat, xr, ur):
-        e, cnt, P, w = self.e, self.count, self.P, self.width
-        t0 = time.perf_counter()
-        zs = np.zeros((4, cnt * P, w), dtype=np.complex128)
-        for b, v in enumerate((xhat, xr, uhat, ur)):
-            v = np.asarray(v, dtype=np.float64).reshape(self.nloops, -1)
-            zs[b, :self.nloops, :v.shape[1]] = v
-        e.enc_pk_packed_batch(self.x.data_ptr(), zs.reshape(4 * cnt, P, w), self.pk, self.s, w, self.scale, self.lvl)
-        part = [self.x.data_ptr() + 8 * b * cnt * self.cw for b in range(4)]
-        e.hempc_step_encgain_packed_batch(self.up.data_ptr(), self.DA, self.DB, part[0], part[1], part[2], part[3],
-                                          cnt, self.lvl, self.rk, self.rlk, self.s, self.rows)
-        uz = e.dec_dcd_packed_batch(self.up.data_ptr(), cnt, self.lvl - 1, self.scale, self.sk, self.s, self.rows)
-        assert np.all(uz.imag < HECTR_SMALL), "imaginary part too large (src/ctr.c:493-494)"
-        self.timings.append(time.perf_counter() - t0)
-        return uz.real.reshape(cnt * P, self.rows)[:self.nloops, :self.problems[0].nu].copy()
+    def _step(self, xhat, xr, uhat, ur):
+        self.e.hempc_step_encgain_packed_batch(self.up.data_ptr(), self.DA, self.DB, xhat, xr, uhat, ur, self.count,
+                                               self.lvl, self.rk, self.rlk, self.s, self.rows)
 
     def close(self):
         self.e.sync()

@@ -183,3 +183,25 @@ def test_gemv_fold_cap_fallback():
     16-diagonal matrix still folds.  Bit-exact against the oracle."""
     res = run_worker("foldcap", {"GPQHE_FOLD_MIB": "256"})
     assert res == {"gemv_batch_dense": 0, "gemv_dense": 0, "gemv_batch_sparse": 0}, res
+
+
+def test_rotation_folds_are_shared_and_evicted():
+    """One rotation key is folded once per level, whichever call needs it:
+    he_rot_batch by the rotations of the rows = 2 product, that product and a
+    dense he_gemv_bsgs_batch on one key array launch gemv_fold_kernel once per
+    distinct (rotation, level), and not again on a second pass.  Under
+    GPQHE_FOLD_MIB=4 (a fold is 2.75 MB at f13's level 6, 2.4 MB at level 5:
+    one fits, the rows call uses four) folds are evicted and made again -- more
+    launches -- and every residue still equals the oracle's."""
+    from tests.bsgs_ref import bsgs_rotations
+    from tests.rows_ref import pow2, rows_rotations
+    a = run_worker("rotfolds", {})
+    s, rows, lvl = a["s"], a["rows"], a["lvl"]
+    rr = rows_rotations(s, rows)
+    pairs = ({(r, lvl) for r in rr} | {(r, lvl if r < pow2(rows) else lvl - 1) for r in rr} |
+             {(r, lvl) for r in bsgs_rotations(s)})
+    assert a["diff"] == 0, a
+    assert a["folds"][0] == len(pairs) and a["folds"][1] == a["folds"][0], (a, len(pairs))
+    b = run_worker("rotfolds", {"GPQHE_FOLD_MIB": "4"})
+    assert b["diff"] == 0, b
+    assert b["folds"][2] > a["folds"][2], (a, b)
