@@ -4,7 +4,7 @@
 // reference src/ctr.c:445-618 and src/hempc.c:216-274 (see gpqhe.h).
 #include "gpqhe_internal.h"
 #include "../../include/gpqhe_ext.h"
-#include "../../include/gpqhe_ext_batch.h"  // (and gpqhe_ext_io_batch.h, gpqhe_ext_step_batch.h, gpqhe_ext_rows_batch.h, gpqhe_ext_packed_batch.h)
+#include "../../include/gpqhe_ext_batch.h"  // (and gpqhe_ext_io_batch.h, gpqhe_ext_step_batch.h, gpqhe_ext_rows_batch.h, gpqhe_ext_packed_batch.h, ..)
 
 #include <math.h>
 #include <stdio.h>
@@ -4160,28 +4160,32 @@ static void io_check(const char *who, unsigned nlimbs, unsigned slots)
     gpqhe_die("%s: bad slot count %u", who, slots);
 }
 
-// P = 0: z [count][s], the vectors as they are encoded.  P > 0 (the packed
-// form, s = P loops' slots): z [count][P][width] loop-major, slot k P + p of
-// ciphertext c from z[c][p][k], 0 for k >= width.
-static void enc_pk_run(const char *who, uint64_t *x, const gpqhe_complex_t z[], size_t count, unsigned s, double scale,
-                       unsigned lvl, const he_pk_t *pk, unsigned P, unsigned width)
+// The encode front end of the batch encryptions, the same under either key:
+// the z upload, the packed gather, the encoder and the one overflow check of a
+// call.  P = 0: z [count][s], the vectors as they are encoded.  P > 0 (the
+// packed form, s = P loops' slots): z [count][P][width] loop-major, slot k P + p
+// of ciphertext c from z[c][p][k], 0 for k >= width.  Takes nstreams RNG
+// streams per ciphertext; chunks sized for key_words words of the caller's
+// workspace per ciphertext next to the encode buffers.  back(c0, cnt, stream,
+// coef): ciphertexts c0 .. c0 + cnt - 1 from their compact coefficients (coef
+// [cnt][2 s], device), `stream` the first of ciphertext c0.
+template <class Back>
+static void enc_front(const char *who, const void *x, const gpqhe_complex_t z[], size_t count, unsigned s, double scale,
+                      unsigned P, unsigned width, unsigned nstreams, size_t key_words, Back back)
 {
-  io_check(who, lvl, s);
-  if (!pk || !pk->data || pk->nlimbs < lvl)
-    gpqhe_die("%s: no public key at level %u", who, lvl);
   if (!count)
     return;
   if (!x || !z)
     gpqhe_die("%s: null argument", who);
-  const size_t n = G.n, w = (size_t)lvl * n, zw = P ? (size_t)P * width : s;  // zw: a ciphertext's values of z
-  // the streams of count he_enc_pk calls: base + 3 i + {0, 1, 2}
+  const size_t zw = P ? (size_t)P * width : s;  // zw: a ciphertext's values of z
+  // the streams of count single encryptions: base + nstreams i + {0, ..}
   const uint64_t base = G.counter;
-  G.counter += 3 * (uint64_t)count;
+  G.counter += nstreams * (uint64_t)count;
   // from gpu_ecd_min() slots the special FFT runs on the GPU (one upload of
   // the chunk's z, staged: at most 64 MiB of it), below it on the host (one
   // upload of the chunk's coefficients)
   const bool gpu = s >= gpu_ecd_min();
-  const size_t per_ct = 3 * w + 2 * (size_t)s * (gpu ? 2 : 1) + (gpu && P ? 2 * zw : 0);
+  const size_t per_ct = key_words + 2 * (size_t)s * (gpu ? 2 : 1) + (gpu && P ? 2 * zw : 0);
   const size_t chunk = io_chunk(count, per_ct, gpu ? std::min<size_t>(16384, ((size_t)4 << 20) / s) : 16384);
   Ws ovf(gpu ? 1 : 0);
   if (gpu)
@@ -4189,7 +4193,7 @@ static void enc_pk_run(const char *who, uint64_t *x, const gpqhe_complex_t z[], 
   std::vector<int64_t> hv;
   for (size_t c0 = 0; c0 < count; c0 += chunk) {
     const unsigned cnt = (unsigned)std::min(chunk, count - c0);
-    Ws vee(3 * cnt * w), coef(2 * (size_t)s * cnt);
+    Ws coef(2 * (size_t)s * cnt);
     const double *zc = (const double *)z + 2 * c0 * zw;
     if (gpu) {
       Ws work(2 * (size_t)s * cnt);
@@ -4215,9 +4219,7 @@ static void enc_pk_run(const char *who, uint64_t *x, const gpqhe_complex_t z[], 
       }
       upload(coef.p, hv.data(), hv.size() * 8);
     }
-    k_enc_sample_batch(vee.p, base + 3 * (uint64_t)c0, (const int64_t *)coef.p, s, lvl, cnt);
-    ntt_polys(vee.p, 3 * (size_t)cnt, lvl, false);
-    k_enc_combine_chunk(x + c0 * 2 * w, vee.p, limb(pk, 0, 0), limb(pk, 1, 0), lvl, cnt);
+    back(c0, cnt, base + nstreams * (uint64_t)c0, (const int64_t *)coef.p);
   }
   if (gpu) {
     // the single encode's overflow check, once for the batch
@@ -4227,6 +4229,43 @@ static void enc_pk_run(const char *who, uint64_t *x, const gpqhe_complex_t z[], 
     if (h)
       gpqhe_die("encode overflow (|value * scale| >= 2^63)");
   }
+}
+
+// he_ecd_ex + he_enc_pk of count vectors (z, P, width: enc_front): per chunk
+// the three noise polynomials of a ciphertext sampled, transformed, combined.
+static void enc_pk_run(const char *who, uint64_t *x, const gpqhe_complex_t z[], size_t count, unsigned s, double scale,
+                       unsigned lvl, const he_pk_t *pk, unsigned P, unsigned width)
+{
+  io_check(who, lvl, s);
+  if (!pk || !pk->data || pk->nlimbs < lvl)
+    gpqhe_die("%s: no public key at level %u", who, lvl);
+  const size_t w = (size_t)lvl * G.n;
+  enc_front(who, x, z, count, s, scale, P, width, 3, 3 * w,
+            [&](size_t c0, unsigned cnt, uint64_t stream, const int64_t *coef) {
+              Ws vee(3 * cnt * w);
+              k_enc_sample_batch(vee.p, stream, coef, s, lvl, cnt);
+              ntt_polys(vee.p, 3 * (size_t)cnt, lvl, false);
+              k_enc_combine_chunk(x + c0 * 2 * w, vee.p, limb(pk, 0, 0), limb(pk, 1, 0), lvl, cnt);
+            });
+}
+
+// he_ecd_ex + he_enc_sk of count vectors (include/gpqhe_ext_sk_batch.h): per
+// chunk c1 sampled where it stays and e + m into the workspace, ONE transform
+// per ciphertext, c0 = NTT(e + m) - c1 s.
+static void enc_sk_run(const char *who, uint64_t *x, const gpqhe_complex_t z[], size_t count, unsigned s, double scale,
+                       unsigned lvl, const poly_mpi_t *sk, unsigned P, unsigned width)
+{
+  io_check(who, lvl, s);
+  if (!sk || !sk->data || sk->nlimbs < lvl)
+    gpqhe_die("%s: no secret key at level %u", who, lvl);
+  const size_t w = (size_t)lvl * G.n;
+  enc_front(who, x, z, count, s, scale, P, width, 2, w,
+            [&](size_t c0, unsigned cnt, uint64_t stream, const int64_t *coef) {
+              Ws E(cnt * w);
+              k_enc_sk_sample_batch(x + c0 * 2 * w, E.p, stream, coef, s, lvl, cnt);
+              ntt_polys(E.p, cnt, lvl, false);
+              k_enc_sk_combine_chunk(x + c0 * 2 * w, E.p, sk->data, lvl, cnt);
+            });
 }
 
 extern "C" void he_enc_pk_batch(uint64_t *x, const gpqhe_complex_t z[], size_t count, unsigned int slots,
@@ -4247,6 +4286,26 @@ extern "C" void he_enc_pk_packed_batch(uint64_t *x, const gpqhe_complex_t z[], s
     gpqhe_die("he_enc_pk_packed_batch: width = %u, s = %u", width, s);
   // (one loop of full width: z is the vector as it is encoded)
   enc_pk_run("he_enc_pk_packed_batch", x, z, count, G.slots, scale, nlimbs, pk, P == 1 && width == s ? 0 : P, width);
+}
+
+extern "C" void he_enc_sk_batch(uint64_t *x, const gpqhe_complex_t z[], size_t count, unsigned int slots,
+                                double scale, unsigned int nlimbs, const poly_mpi_t *sk)
+{
+  HPROF("enc_sk_batch");
+  check_ctx();
+  enc_sk_run("he_enc_sk_batch", x, z, count, slots, scale, nlimbs, sk, 0, 0);
+}
+
+extern "C" void he_enc_sk_packed_batch(uint64_t *x, const gpqhe_complex_t z[], size_t count, unsigned int s,
+                                       unsigned int width, double scale, unsigned int nlimbs, const poly_mpi_t *sk)
+{
+  HPROF("enc_sk_packed_batch");
+  check_ctx();
+  const unsigned P = packed_loops("he_enc_sk_packed_batch", s);
+  if (!width || width > s)
+    gpqhe_die("he_enc_sk_packed_batch: width = %u, s = %u", width, s);
+  // (one loop of full width: z is the vector as it is encoded)
+  enc_sk_run("he_enc_sk_packed_batch", x, z, count, G.slots, scale, nlimbs, sk, P == 1 && width == s ? 0 : P, width);
 }
 
 // The folded path (k_dec_fold, k_fold_decode) reads each ciphertext once and
@@ -4343,24 +4402,43 @@ extern "C" void he_dec_dcd_packed_batch(gpqhe_complex_t z[], const uint64_t *y, 
 // its tensor is (0, 0, X2)) and the fold: one key switch more than the packed
 // step, whatever m'.  Nothing is encoded, so there is no plan.
 // ---------------------------------------------------------------------------
-extern "C" void he_enc_gain_packed_batch(uint64_t *D, const gpqhe_complex_t M[], unsigned int s, unsigned int rows,
-                                         unsigned int nmat, unsigned int nlimbs, const he_pk_t *pk)
+// every E_i of M, the all-zero ones too (which diagonals vanish stays with the
+// client), as enc_pk_run / enc_sk_run read them: [m'][S] complex values
+static std::vector<double> gain_diags(const char *who, const gpqhe_complex_t M[], unsigned s, unsigned rows,
+                                      unsigned nmat, unsigned nlimbs, unsigned &mp)
 {
-  HPROF("enc_gain_packed_batch");
-  const char *who = "he_enc_gain_packed_batch";
   check_ctx();
   rows_loops(who, s, rows, nmat);
   io_check(who, nlimbs, G.slots);
   if (!M)
     gpqhe_die("%s: null argument", who);
-  // every E_i, the all-zero ones too: which diagonals vanish stays with the client
-  const unsigned mp = rows_pow2(rows);
+  mp = rows_pow2(rows);
   std::vector<double> E(2 * (size_t)mp * G.slots), v(2 * (size_t)G.slots);
   for (unsigned i = 0; i < mp; i++) {
     rows_diag(v, (const double *)M, i, rows, mp, s, nmat);
     std::copy(v.begin(), v.end(), E.begin() + 2 * (size_t)i * G.slots);
   }
+  return E;
+}
+
+extern "C" void he_enc_gain_packed_batch(uint64_t *D, const gpqhe_complex_t M[], unsigned int s, unsigned int rows,
+                                         unsigned int nmat, unsigned int nlimbs, const he_pk_t *pk)
+{
+  HPROF("enc_gain_packed_batch");
+  const char *who = "he_enc_gain_packed_batch";
+  unsigned mp;
+  const std::vector<double> E = gain_diags(who, M, s, rows, nmat, nlimbs, mp);
   enc_pk_run(who, D, (const gpqhe_complex_t *)E.data(), mp, G.slots, (double)G.q[nlimbs - 1], nlimbs, pk, 0, 0);
+}
+
+extern "C" void he_enc_gain_sk_packed_batch(uint64_t *D, const gpqhe_complex_t M[], unsigned int s, unsigned int rows,
+                                            unsigned int nmat, unsigned int nlimbs, const poly_mpi_t *sk)
+{
+  HPROF("enc_gain_sk_packed_batch");
+  const char *who = "he_enc_gain_sk_packed_batch";
+  unsigned mp;
+  const std::vector<double> E = gain_diags(who, M, s, rows, nmat, nlimbs, mp);
+  enc_sk_run(who, D, (const gpqhe_complex_t *)E.data(), mp, G.slots, (double)G.q[nlimbs - 1], nlimbs, sk, 0, 0);
 }
 
 // One chunk of cnt ciphertexts.  W: 2 (m' - 1) + 3 (+ 2 with st) slots of cnt

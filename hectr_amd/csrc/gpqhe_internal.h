@@ -117,6 +117,15 @@ __host__ __device__ __forceinline__ uint64_t reduce64(uint64_t x, const ModConst
   return r >= m.q ? r - m.q : r;
 }
 
+// v mod q for a signed 64-bit v (an encoded coefficient)
+__host__ __device__ __forceinline__ uint64_t lift_i64(int64_t v, const ModConst &c)
+{
+  if (v >= 0)
+    return reduce64((uint64_t)v, c);
+  const uint64_t r = reduce64((uint64_t)(-(v + 1)), c) + 1;  // |v| mod q in [1, q]
+  return r == c.q ? 0 : c.q - r;
+}
+
 // ---------------------------------------------------------------------------
 // ChaCha20 block (state: constants | key | counter | 0 | stream lo | hi).
 // ---------------------------------------------------------------------------
@@ -479,7 +488,7 @@ enum KClass {
   KC_BSGS_SUM, KC_BSGS_INNER_BATCH, KC_BSGS_SUM_BATCH, KC_FFT_ENC_BATCH, KC_ENC_SAMPLE_BATCH, KC_ENC_COMBINE_BATCH,
   KC_DEC_FOLD, KC_FOLD_DCD, KC_DEC_BATCH, KC_STEP_DIFF_BATCH, KC_STEP_TAIL_BATCH,
   KC_ROWS_FOLD_ADD_BATCH, KC_ROWS_FOLD_TAIL_BATCH, KC_PACK_ENC_GATHER, KC_PACK_DCD_GATHER, KC_FOLD_DCD_PACKED,
-  KC_FFT_DEC_PACKED, KC_ENCGAIN_TENSOR, KC_ENCGAIN_ONES, KC_COUNT
+  KC_FFT_DEC_PACKED, KC_ENCGAIN_TENSOR, KC_ENCGAIN_ONES, KC_ENC_SK_SAMPLE_BATCH, KC_ENC_SK_COMBINE_BATCH, KC_COUNT
 };
 struct ProfScope {
   int cls;
@@ -609,6 +618,18 @@ void k_encgain_tensor(uint64_t *X01, uint64_t *Q, const uint64_t *xa, const uint
                       unsigned cnt);
 // one [cnt][2][lvl][n] <- the ciphertext (0, 1) of every pair
 void k_encgain_ones(uint64_t *one, unsigned lvl, unsigned cnt);
+// he_enc_sk_batch and its packed forms (sk_batch.hip) over a chunk of cnt
+// ciphertexts x [cnt][2][nl][n].  Ciphertexts per workgroup of the batch
+// combines (the key words stay in registers across them):
+constexpr unsigned IOB_CG = 8;
+// E [cnt][nl][n] <- e + m of ciphertext i, e the CBD sample of ChaCha stream
+// stream + 2 i + 1 and m from coef (device, k_enc_sample_batch's layout), in
+// coefficient form; x[i][1] <- the uniform sample of stream + 2 i
+// (k_sample_uniform's values)
+void k_enc_sk_sample_batch(uint64_t *x, uint64_t *E, uint64_t stream, const int64_t *coef, unsigned s, unsigned nl,
+                           unsigned cnt);
+// x[i][0] <- E_i - x[i][1] sk of the transformed E
+void k_enc_sk_combine_chunk(uint64_t *x, const uint64_t *E, const uint64_t *sk, unsigned nl, unsigned cnt);
 void tables_upload();
 void tables_prewarm();
 void tables_free();

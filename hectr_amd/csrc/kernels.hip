@@ -53,7 +53,8 @@ static const char *kc_names[KC_COUNT] = {
   "fft_enc_batch_kernel", "enc_sample_batch_kernel", "enc_combine_batch_kernel", "dec_fold_kernel",
   "fold_dcd_kernel", "dec_batch_kernel", "step_diff_batch_kernel", "step_tail_batch_kernel",
   "rows_fold_add_batch_kernel", "rows_fold_tail_batch_kernel", "pack_enc_gather_kernel", "pack_dcd_gather_kernel",
-  "fold_dcd_packed_kernel", "fft_dec_lds_packed_kernel", "encgain_tensor_kernel", "encgain_ones_kernel"};
+  "fold_dcd_packed_kernel", "fft_dec_lds_packed_kernel", "encgain_tensor_kernel", "encgain_ones_kernel",
+  "enc_sk_sample_batch_kernel", "enc_sk_combine_batch_kernel"};
 
 struct ProfEntry {
   int cls;
@@ -638,14 +639,6 @@ void k_ntt_rows(const LimbSet &in, const LimbSet &out, bool inverse)
 // coef != nullptr (forward only): round 0 reads the signed integer
 // coefficients shared by every limb and lifts them mod q (encoding), instead
 // of a separate lift launch.
-__device__ __forceinline__ uint64_t lift_i64(int64_t v, const ModConst &c)
-{
-  if (v >= 0)
-    return reduce64((uint64_t)v, c);
-  const uint64_t r = reduce64((uint64_t)(-(v + 1)), c) + 1;  // |v| mod q in [1, q]
-  return r == c.q ? 0 : c.q - r;
-}
-
 // small_fwd / small_inv: ntt_device.h
 
 template <int LOGN, bool INV>
@@ -4351,8 +4344,6 @@ void k_enc_sample_batch(uint64_t *vee, uint64_t stream, const int64_t *coef, uns
 
 // enc_batch_kernel (m already in e0) into the batch layout: a workgroup holds
 // its public-key words in registers across IOB_CG ciphertexts.
-constexpr unsigned IOB_CG = 8;
-
 __global__ void enc_combine_batch_kernel(uint64_t *x, const uint64_t *vee, const uint64_t *pk0, const uint64_t *pk1,
                                          unsigned logn, unsigned nl, unsigned cnt, const ModConst *mc)
 {

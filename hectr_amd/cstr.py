@@ -483,11 +483,13 @@ class BatchedEncryptedRegulator(_BatchRegulator):
     the problem's gain matrices, the key pair and the he_genrk_bsgs(g) rotation
     keys.  With rows=k (k >= nu: only the first nu entries of the result are
     used) the step is he_hempc_step_rows_batch, the row-folded product of the k
-    leading rows, on the he_genrk_rows(k) keys.  Device memory comes from torch."""
+    leading rows, on the he_genrk_rows(k) keys.  With sym=True the encrypting
+    party uses its secret key: he_enc_sk_batch (include/gpqhe_ext_sk_batch.h).
+    Device memory comes from torch."""
 
     def __init__(self, engine, problem: CstrProblem, count, g=0, seed=None, logn=12, logq=109, log_delta=50,
-                 init=True, rows=None):
-        self.pb, self.g, self.rows = problem, g, rows
+                 init=True, rows=None, sym=False):
+        self.pb, self.g, self.rows, self.sym = problem, g, rows, sym
         assert rows is None or problem.nu <= rows <= problem.slots
         s = problem.slots
         self._setup(engine, s, count, (count, count, s), problem.nu, seed, logn, logq, log_delta, init)
@@ -502,6 +504,9 @@ class BatchedEncryptedRegulator(_BatchRegulator):
 
     def _enc(self, zs):
         s = self.pb.slots
+        if self.sym:
+            self.e.enc_sk_batch(self.x.data_ptr(), zs.reshape(4 * self.count, s), self.sk, s, self.scale, self.lvl)
+            return
         self.e.enc_pk_batch(self.x.data_ptr(), zs.reshape(4 * self.count, s), self.pk, s, self.scale, self.lvl)
 
     def _step(self, xhat, xr, uhat, ur):
@@ -526,12 +531,15 @@ class PackedEncryptedRegulator(_BatchRegulator):
     he_dec_dcd_packed_batch.  Loop p uses its own problem's MA / MB (nmat = P;
     loop p of every ciphertext the same, so with several ciphertexts the
     problems P apart must share their gains), or one shared pair (nmat = 1)
-    when all problems are one object.  __call__ is BatchedEncryptedRegulator's:
-    [len(problems)][.] arrays in, u [len(problems)][nu] out."""
+    when all problems are one object.  With sym=True the encryption is
+    he_enc_sk_packed_batch (include/gpqhe_ext_sk_batch.h).  __call__ is
+    BatchedEncryptedRegulator's: [len(problems)][.] arrays in, u
+    [len(problems)][nu] out."""
 
     def __init__(self, engine, problems, slots_total, rows=None, seed=None, logn=12, logq=109, log_delta=50,
-                 init=True):
+                 init=True, sym=False):
         pb = problems[0]
+        self.sym = sym
         s = pb.slots
         self.problems, self.s, self.S = list(problems), s, slots_total
         self.rows = pb.nu if rows is None else rows
@@ -565,6 +573,10 @@ class PackedEncryptedRegulator(_BatchRegulator):
         self.e.genrk_packed(self.rk, self.sk, self.s, self.rows)
 
     def _enc(self, zs):
+        if self.sym:
+            self.e.enc_sk_packed_batch(self.x.data_ptr(), zs.reshape(4 * self.count, self.P, self.width), self.sk,
+                                       self.s, self.width, self.scale, self.lvl)
+            return
         self.e.enc_pk_packed_batch(self.x.data_ptr(), zs.reshape(4 * self.count, self.P, self.width), self.pk, self.s,
                                    self.width, self.scale, self.lvl)
 
@@ -584,12 +596,14 @@ class EncryptedGainRegulator(PackedEncryptedRegulator):
     constructor makes the relinearisation key and encrypts the m' extended
     diagonals of MA and of MB once (he_enc_gain_packed_batch, MA first); every
     step is he_hempc_step_encgain_packed_batch on those two ciphertext sets.
-    Packing, keys, encryption and decode are the parent's."""
+    Packing, keys, encryption and decode are the parent's.  With sym=True the
+    diagonals too are encrypted under the secret key
+    (he_enc_gain_sk_packed_batch)."""
 
     def __init__(self, engine, problems, slots_total, rows=None, seed=None, logn=12, logq=109, log_delta=50,
-                 init=True):
+                 init=True, sym=False):
         import torch
-        super().__init__(engine, problems, slots_total, rows, seed, logn, logq, log_delta, init)
+        super().__init__(engine, problems, slots_total, rows, seed, logn, logq, log_delta, init, sym)
         self.rlk = engine.evk()
         engine.genrlk(self.rlk, self.sk)
         mp = 1
@@ -599,6 +613,10 @@ class EncryptedGainRegulator(PackedEncryptedRegulator):
         self.D = torch.zeros(2 * mp * self.cw, dtype=torch.int64, device="cuda")
         torch.cuda.synchronize()
         self.DA, self.DB = self.D.data_ptr(), self.D.data_ptr() + 8 * mp * self.cw
+        if sym:
+            engine.enc_gain_sk_packed_batch(self.DA, self.MAz, self.sk, self.s, self.rows, self.lvl, self.nmat)
+            engine.enc_gain_sk_packed_batch(self.DB, self.MBz, self.sk, self.s, self.rows, self.lvl, self.nmat)
+            return
         engine.enc_gain_packed_batch(self.DA, self.MAz, self.pk, self.s, self.rows, self.lvl, self.nmat)
         engine.enc_gain_packed_batch(self.DB, self.MBz, self.pk, self.s, self.rows, self.lvl, self.nmat)
 

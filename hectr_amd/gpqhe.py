@@ -206,6 +206,14 @@ PRODUCT_EXT_ENCGAIN_BATCH = {
                                                   C.c_uint, C.c_uint]),
 }
 
+#: include/gpqhe_ext_sk_batch.h (part of gpqhe_ext_batch.h): the batch
+#: encryptions under the secret key, product only, bound like PRODUCT_EXT
+PRODUCT_EXT_SK_BATCH = {
+    "he_enc_sk_batch": (None, [VP, VP, C.c_size_t, C.c_uint, C.c_double, C.c_uint, OBJ]),
+    "he_enc_sk_packed_batch": (None, [VP, VP, C.c_size_t, C.c_uint, C.c_uint, C.c_double, C.c_uint, OBJ]),
+    "he_enc_gain_sk_packed_batch": (None, [VP, VP, C.c_uint, C.c_uint, C.c_uint, C.c_uint, OBJ]),
+}
+
 
 def _cplx(z) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(z, dtype=np.complex128))
@@ -229,7 +237,8 @@ class Engine:
             f.argtypes = args
         for sym, (res, args) in {**PRODUCT_EXT, **PRODUCT_EXT_BATCH, **PRODUCT_EXT_IO_BATCH,
                                  **PRODUCT_EXT_STEP_BATCH, **PRODUCT_EXT_ROWS_BATCH,
-                                 **PRODUCT_EXT_PACKED_BATCH, **PRODUCT_EXT_ENCGAIN_BATCH}.items():
+                                 **PRODUCT_EXT_PACKED_BATCH, **PRODUCT_EXT_ENCGAIN_BATCH,
+                                 **PRODUCT_EXT_SK_BATCH}.items():
             if hasattr(self.lib, sym):  # not the oracle, nor an older library under GPQHE_LIB
                 f = getattr(self.lib, sym)
                 f.restype = res
@@ -501,6 +510,29 @@ class Engine:
         memory x_ptr [count][2][nlimbs][n] (include/gpqhe_ext_batch.h)."""
         zs = _cplx(zs).reshape(-1, slots)
         self._ext("he_enc_pk_batch")(x_ptr, zs.ctypes.data, zs.shape[0], slots, scale, nlimbs, C.byref(pk))
+
+    def enc_sk_batch(self, x_ptr, zs, sk, slots, scale, nlimbs):
+        """he_ecd_ex + he_enc_sk of the rows of zs [count][slots] into device
+        memory x_ptr [count][2][nlimbs][n] (include/gpqhe_ext_sk_batch.h)."""
+        zs = _cplx(zs).reshape(-1, slots)
+        self._ext("he_enc_sk_batch")(x_ptr, zs.ctypes.data, zs.shape[0], slots, scale, nlimbs, C.byref(sk))
+
+    def enc_sk_packed_batch(self, x_ptr, zs, sk, s, width, scale, nlimbs):
+        """enc_pk_packed_batch under the secret key: he_ecd_ex + he_enc_sk of zs
+        [count][slots / s][width] (loop-major, entries past width zero) into
+        device memory x_ptr [count][2][nlimbs][n] (include/gpqhe_ext_sk_batch.h)."""
+        f = self._ext("he_enc_sk_packed_batch")
+        zs = _cplx(zs).reshape(-1, self.slots // s, width)
+        f(x_ptr, zs.ctypes.data, zs.shape[0], s, width, scale, nlimbs, C.byref(sk))
+
+    def enc_gain_sk_packed_batch(self, d_ptr, M, sk, s, rows, nlimbs, nmat=1):
+        """enc_gain_packed_batch under the secret key: all m' extended diagonals
+        of M [nmat][rows][s] encrypted at scale q_top into device memory d_ptr
+        [m'][2][nlimbs][n] (include/gpqhe_ext_sk_batch.h)."""
+        f = self._ext("he_enc_gain_sk_packed_batch")
+        M = _cplx(M)
+        assert M.size >= nmat * rows * s
+        f(d_ptr, M.ctypes.data, s, rows, nmat, nlimbs, C.byref(sk))
 
     def dec_dcd_batch(self, y_ptr, count, nlimbs, scale, sk, slots):
         """he_dec + he_dcd_ex of `count` ciphertexts in device memory y_ptr

@@ -39,5 +39,7 @@ void he_gemv_bsgs_batch(uint64_t *y, const gpqhe_complex_t M[], const uint64_t *
 #include "gpqhe_ext_packed_batch.h"
 /* the packed step with the gains encrypted: ct x ct and one relinearisation */
 #include "gpqhe_ext_encgain_batch.h"
+/* the encrypting end under the secret key: one transform per ciphertext */
+#include "gpqhe_ext_sk_batch.h"
 
 #endif /* GPQHE_EXT_BATCH_H */
