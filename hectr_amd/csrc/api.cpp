@@ -4308,6 +4308,93 @@ extern "C" void he_enc_sk_packed_batch(uint64_t *x, const gpqhe_complex_t z[], s
   enc_sk_run("he_enc_sk_packed_batch", x, z, count, G.slots, scale, nlimbs, sk, P == 1 && width == s ? 0 : P, width);
 }
 
+// ---------------------------------------------------------------------------
+// he_enc_sk_seeded_batch and its packed forms, he_expand_seeded_batch
+// (include/gpqhe_ext_seeded_batch.h): c1 is the uniform sample of a PUBLIC
+// ChaCha key and stream, never stored by the encrypting side.
+// ---------------------------------------------------------------------------
+static ChachaKey seeded_key(const char *who, const gpqhe_pubseed_t *ps, size_t count)
+{
+  if (!ps)
+    gpqhe_die("%s: null seed", who);
+  if (ps->stream + (uint64_t)count < ps->stream)
+    gpqhe_die("%s: the seed's stream %llu + %zu ciphertexts wraps 2^64", who, (unsigned long long)ps->stream, count);
+  ChachaKey k;
+  for (unsigned i = 0; i < 8; i++)
+    k.k[i] = ps->key[i];
+  return k;
+}
+
+// enc_sk_run with c1 kept in registers: per chunk e + m sampled straight into
+// the compact output (private stream base + 2 i + 1; base + 2 i is skipped),
+// transformed there, and c0 = NTT(e + m) - a s finished in place, a from the
+// public stream ps->stream + i.  No ciphertext workspace.
+static void enc_sk_seeded_run(const char *who, uint64_t *c0, const gpqhe_complex_t z[], size_t count, unsigned s,
+                              double scale, unsigned lvl, const poly_mpi_t *sk, unsigned P, unsigned width,
+                              gpqhe_pubseed_t *ps)
+{
+  io_check(who, lvl, s);
+  if (!sk || !sk->data || sk->nlimbs < lvl)
+    gpqhe_die("%s: no secret key at level %u", who, lvl);
+  const ChachaKey pub = seeded_key(who, ps, count);
+  const uint64_t pstream = ps->stream;
+  const size_t w = (size_t)lvl * G.n;
+  enc_front(who, c0, z, count, s, scale, P, width, 2, 0,
+            [&](size_t i0, unsigned cnt, uint64_t stream, const int64_t *coef) {
+              uint64_t *o = c0 + i0 * w;
+              k_enc_sk_sample_batch(nullptr, o, stream, coef, s, lvl, cnt, true);
+              ntt_polys(o, cnt, lvl, false);
+              k_enc_sk_seeded_combine(o, sk->data, pub, pstream + i0, lvl, cnt);
+            });
+  ps->stream += count;
+}
+
+extern "C" void he_enc_sk_seeded_batch(uint64_t *c0, const gpqhe_complex_t z[], size_t count, unsigned int slots,
+                                       double scale, unsigned int nlimbs, const poly_mpi_t *sk, gpqhe_pubseed_t *ps)
+{
+  HPROF("enc_sk_seeded_batch");
+  check_ctx();
+  enc_sk_seeded_run("he_enc_sk_seeded_batch", c0, z, count, slots, scale, nlimbs, sk, 0, 0, ps);
+}
+
+extern "C" void he_enc_sk_seeded_packed_batch(uint64_t *c0, const gpqhe_complex_t z[], size_t count, unsigned int s,
+                                              unsigned int width, double scale, unsigned int nlimbs,
+                                              const poly_mpi_t *sk, gpqhe_pubseed_t *ps)
+{
+  HPROF("enc_sk_seeded_packed_batch");
+  check_ctx();
+  const unsigned P = packed_loops("he_enc_sk_seeded_packed_batch", s);
+  if (!width || width > s)
+    gpqhe_die("he_enc_sk_seeded_packed_batch: width = %u, s = %u", width, s);
+  // (one loop of full width: z is the vector as it is encoded)
+  enc_sk_seeded_run("he_enc_sk_seeded_packed_batch", c0, z, count, G.slots, scale, nlimbs, sk,
+                    P == 1 && width == s ? 0 : P, width, ps);
+}
+
+// x [count][2][nlimbs][n] <- (c0 [count][nlimbs][n], the samples of ps): no
+// key, no private stream, no workspace; chunks only for the grid's limits
+extern "C" void he_expand_seeded_batch(uint64_t *x, const uint64_t *c0, size_t count, unsigned int nlimbs,
+                                       const gpqhe_pubseed_t *ps)
+{
+  HPROF("expand_seeded_batch");
+  const char *who = "he_expand_seeded_batch";
+  check_ctx();
+  if (nlimbs < 1 || nlimbs > G.L)
+    gpqhe_die("%s: bad level %u", who, nlimbs);
+  const ChachaKey pub = seeded_key(who, ps, count);
+  if (!count)
+    return;
+  if (!x || !c0)
+    gpqhe_die("%s: null argument", who);
+  const size_t w = (size_t)nlimbs * G.n;
+  const uintptr_t xa = (uintptr_t)x, ca = (uintptr_t)c0;
+  if (xa < ca + 8 * count * w && ca < xa + 16 * count * w)
+    gpqhe_die("%s: x overlaps c0", who);
+  const size_t chunk = io_chunk(count, 1, 16384);
+  for (size_t i0 = 0; i0 < count; i0 += chunk)
+    k_seeded_expand(x + i0 * 2 * w, c0 + i0 * w, pub, ps->stream + i0, nlimbs, (unsigned)std::min(chunk, count - i0));
+}
+
 // The folded path (k_dec_fold, k_fold_decode) reads each ciphertext once and
 // transforms 2 slots points per limb; it needs a gap n / 2 slots >= 2 and the
 // one-workgroup decoder.  Otherwise, and under GPQHE_DCD_FOLD=0: c0 + c1 s of
@@ -4439,6 +4526,18 @@ extern "C" void he_enc_gain_sk_packed_batch(uint64_t *D, const gpqhe_complex_t M
   unsigned mp;
   const std::vector<double> E = gain_diags(who, M, s, rows, nmat, nlimbs, mp);
   enc_sk_run(who, D, (const gpqhe_complex_t *)E.data(), mp, G.slots, (double)G.q[nlimbs - 1], nlimbs, sk, 0, 0);
+}
+
+extern "C" void he_enc_gain_sk_seeded_packed_batch(uint64_t *D0, const gpqhe_complex_t M[], unsigned int s,
+                                                   unsigned int rows, unsigned int nmat, unsigned int nlimbs,
+                                                   const poly_mpi_t *sk, gpqhe_pubseed_t *ps)
+{
+  HPROF("enc_gain_sk_seeded_packed_batch");
+  const char *who = "he_enc_gain_sk_seeded_packed_batch";
+  unsigned mp;
+  const std::vector<double> E = gain_diags(who, M, s, rows, nmat, nlimbs, mp);
+  enc_sk_seeded_run(who, D0, (const gpqhe_complex_t *)E.data(), mp, G.slots, (double)G.q[nlimbs - 1], nlimbs, sk, 0,
+                    0, ps);
 }
 
 // One chunk of cnt ciphertexts.  W: 2 (m' - 1) + 3 (+ 2 with st) slots of cnt

@@ -488,7 +488,8 @@ enum KClass {
   KC_BSGS_SUM, KC_BSGS_INNER_BATCH, KC_BSGS_SUM_BATCH, KC_FFT_ENC_BATCH, KC_ENC_SAMPLE_BATCH, KC_ENC_COMBINE_BATCH,
   KC_DEC_FOLD, KC_FOLD_DCD, KC_DEC_BATCH, KC_STEP_DIFF_BATCH, KC_STEP_TAIL_BATCH,
   KC_ROWS_FOLD_ADD_BATCH, KC_ROWS_FOLD_TAIL_BATCH, KC_PACK_ENC_GATHER, KC_PACK_DCD_GATHER, KC_FOLD_DCD_PACKED,
-  KC_FFT_DEC_PACKED, KC_ENCGAIN_TENSOR, KC_ENCGAIN_ONES, KC_ENC_SK_SAMPLE_BATCH, KC_ENC_SK_COMBINE_BATCH, KC_COUNT
+  KC_FFT_DEC_PACKED, KC_ENCGAIN_TENSOR, KC_ENCGAIN_ONES, KC_ENC_SK_SAMPLE_BATCH, KC_ENC_SK_COMBINE_BATCH,
+  KC_ENC_SK_SEEDED_COMBINE, KC_SEEDED_EXPAND, KC_COUNT
 };
 struct ProfScope {
   int cls;
@@ -625,11 +626,20 @@ constexpr unsigned IOB_CG = 8;
 // E [cnt][nl][n] <- e + m of ciphertext i, e the CBD sample of ChaCha stream
 // stream + 2 i + 1 and m from coef (device, k_enc_sample_batch's layout), in
 // coefficient form; x[i][1] <- the uniform sample of stream + 2 i
-// (k_sample_uniform's values)
+// (k_sample_uniform's values); noise_only: E alone, x unread (the seeded form)
 void k_enc_sk_sample_batch(uint64_t *x, uint64_t *E, uint64_t stream, const int64_t *coef, unsigned s, unsigned nl,
-                           unsigned cnt);
+                           unsigned cnt, bool noise_only = false);
 // x[i][0] <- E_i - x[i][1] sk of the transformed E
 void k_enc_sk_combine_chunk(uint64_t *x, const uint64_t *E, const uint64_t *sk, unsigned nl, unsigned cnt);
+// he_enc_sk_seeded_batch and he_expand_seeded_batch (seeded_batch.hip) over a
+// chunk of cnt ciphertexts; a: the uniform sample of ciphertext i under the
+// PUBLIC ChaCha key pub and stream pstream + i (k_sample_uniform's map).
+// c0 [cnt][nl][n] <- c0 - a sk in place (c0: the transformed e + m); a is never stored
+void k_enc_sk_seeded_combine(uint64_t *c0, const uint64_t *sk, const ChachaKey &pub, uint64_t pstream, unsigned nl,
+                             unsigned cnt);
+// x [cnt][2][nl][n] <- (c0 [cnt][nl][n], a); x and c0 do not overlap
+void k_seeded_expand(uint64_t *x, const uint64_t *c0, const ChachaKey &pub, uint64_t pstream, unsigned nl,
+                     unsigned cnt);
 void tables_upload();
 void tables_prewarm();
 void tables_free();

@@ -54,7 +54,8 @@ static const char *kc_names[KC_COUNT] = {
   "fold_dcd_kernel", "dec_batch_kernel", "step_diff_batch_kernel", "step_tail_batch_kernel",
   "rows_fold_add_batch_kernel", "rows_fold_tail_batch_kernel", "pack_enc_gather_kernel", "pack_dcd_gather_kernel",
   "fold_dcd_packed_kernel", "fft_dec_lds_packed_kernel", "encgain_tensor_kernel", "encgain_ones_kernel",
-  "enc_sk_sample_batch_kernel", "enc_sk_combine_batch_kernel"};
+  "enc_sk_sample_batch_kernel", "enc_sk_combine_batch_kernel", "enc_sk_seeded_combine_kernel",
+  "seeded_expand_kernel"};
 
 struct ProfEntry {
   int cls;

@@ -415,6 +415,35 @@ __device__ __forceinline__ uint64_t mulc_canon(uint64_t x, uint64_t w, uint64_t 
 }
 constexpr uint64_t F64_LAZY = 1ull << 50;  // and its lazy stage reduction below this
 
+// fl(1 / q_l) of the context's moduli, by value: a limb's is wave-uniform, so
+// no thread divides
+struct SkQinv {
+  double v[GPQHE_MAXMOD];
+};
+
+// A limb of a uniform sample from its quarter of a ChaCha block (sk_batch.hip,
+// seeded_batch.hip; sample_uniform_kernel's values): the words w[0 .. 3] as a
+// 128-bit little-endian integer mod q, canonical.  Below 2^51 by an exact FP64
+// Horner rule over the 32-bit words (qinv = fl(1 / q)), otherwise by Barrett
+// with 2^64 mod q from the limb's constants.
+__device__ __forceinline__ uint64_t chacha_u128_mod(const uint32_t *w, const ModConst &m, double qinv)
+{
+  if (m.q < F64_QMAX) {
+    // a product by 2^32 is exact before its reduction, so f64_mulmod_h returns
+    // an integer of at most q / 2 (+ 2^-20 q), and adding a word keeps it
+    // below 2^53
+    const double q = (double)m.q;
+    double r = f64_red((double)w[3], q, qinv);
+    r = f64_red(f64_mulmod_h(r, 0x1p32, q, qinv) + (double)w[2], q, qinv);
+    r = f64_red(f64_mulmod_h(r, 0x1p32, q, qinv) + (double)w[1], q, qinv);
+    return f64_canon(f64_mulmod_h(r, 0x1p32, q, qinv) + (double)w[0], q, qinv);
+  }
+  const uint64_t lo = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
+  const uint64_t hi = (uint64_t)w[2] | ((uint64_t)w[3] << 32);
+  // (hi 2^64 + lo) mod q
+  return add_mod(mul_mod(reduce64(hi, m), m.r64, m), reduce64(lo, m), m.q);
+}
+
 // Forward row passes with the twiddles of one row tile staged in LDS.  A
 // 2^LOGN2-point row pass of global row rho uses, at its stage of level lam
 // (0 .. LOGN2-1), the 2^lam twiddles tw[rho 2^lam + g]; the R rows

@@ -14,12 +14,6 @@
 
 typedef unsigned long long sk_u2 __attribute__((ext_vector_type(2)));
 
-// fl(1 / q_l) of the context's moduli, by value: a limb's is wave-uniform, so
-// no thread divides
-struct SkQinv {
-  double v[GPQHE_MAXMOD];
-};
-
 // grid: (n / TPB, cnt, 1 + ceil(nl / 4)); one coefficient k of ciphertext
 // c = blockIdx.y per thread.
 // z = 0: the noise.  enc_sample_batch_kernel's e0 branch for one polynomial per
@@ -29,8 +23,8 @@ struct SkQinv {
 // z = 1 + j: limbs 4 j .. 4 j + 3 of c1 from ONE block, k nb + j of stream
 // `stream + 2 c` (sample_uniform_kernel's values; it computes the block once
 // per limb): words 4 t .. 4 t + 3 as a 128-bit little-endian integer mod
-// q_(4 j + t): below 2^51 by an exact FP64 Horner rule over the 32-bit words,
-// otherwise by Barrett with 2^64 mod q from the limb's constants.
+// q_(4 j + t) (chacha_u128_mod).  A grid of depth 1 runs the noise alone (the
+// seeded form, seeded_batch.hip: x unread).
 __global__ void __launch_bounds__(TPB)
   enc_sk_sample_batch_kernel(uint64_t *x, uint64_t *E, unsigned logn, unsigned nl, unsigned nb, ChachaKey key,
                              uint64_t stream, const int64_t *coef, unsigned logT, unsigned m2, const ModConst *mc,
@@ -64,40 +58,24 @@ __global__ void __launch_bounds__(TPB)
     const unsigned l = 4 * j + t;
     if (l >= nl)  // (workgroup-uniform)
       break;
-    const ModConst &m = mc[l];
-    uint64_t v;
-    if (m.q < F64_QMAX) {  // (workgroup-uniform)
-      // Horner over the four 32-bit words in exact FP64: a product by 2^32 is
-      // exact before its reduction, so f64_mulmod_h returns an integer of at
-      // most q / 2 (+ 2^-20 q), and adding a word keeps it below 2^53
-      const double q = (double)m.q, qinv = qi.v[l];
-      double r = f64_red((double)b[4 * t + 3], q, qinv);
-      r = f64_red(f64_mulmod_h(r, 0x1p32, q, qinv) + (double)b[4 * t + 2], q, qinv);
-      r = f64_red(f64_mulmod_h(r, 0x1p32, q, qinv) + (double)b[4 * t + 1], q, qinv);
-      v = f64_canon(f64_mulmod_h(r, 0x1p32, q, qinv) + (double)b[4 * t], q, qinv);
-    } else {
-      const uint64_t lo = (uint64_t)b[4 * t] | ((uint64_t)b[4 * t + 1] << 32);
-      const uint64_t hi = (uint64_t)b[4 * t + 2] | ((uint64_t)b[4 * t + 3] << 32);
-      // (hi 2^64 + lo) mod q
-      v = add_mod(mul_mod(reduce64(hi, m), m.r64, m), reduce64(lo, m), m.q);
-    }
-    dst[(size_t)l << logn] = v;
+    dst[(size_t)l << logn] = chacha_u128_mod(b + 4 * t, mc[l], qi.v[l]);
   }
 }
 
 void k_enc_sk_sample_batch(uint64_t *x, uint64_t *E, uint64_t stream, const int64_t *coef, unsigned s, unsigned nl,
-                           unsigned cnt)
+                           unsigned cnt, bool noise_only)
 {
   if (!cnt || cnt > 65535 || !nl || nl > G.L)
     gpqhe_die("k_enc_sk_sample_batch: %u ciphertexts at level %u in one chunk", cnt, nl);
   const unsigned logT = G.logn - 1 - (unsigned)__builtin_ctz(s);
-  // both polynomials written, the compact coefficients read
-  ProfScope ps(KC_ENC_SK_SAMPLE_BATCH, 8.0 * G.n * nl * 2 * cnt + 16.0 * s * cnt);
+  // both polynomials (noise_only: E alone) written, the compact coefficients read
+  ProfScope ps(KC_ENC_SK_SAMPLE_BATCH, 8.0 * G.n * nl * (noise_only ? 1 : 2) * cnt + 16.0 * s * cnt);
   SkQinv qi;
   for (unsigned l = 0; l < GPQHE_MAXMOD; l++)
     qi.v[l] = l < nl ? 1.0 / (double)G.q[l] : 0.0;
-  hipLaunchKernelGGL(enc_sk_sample_batch_kernel, dim3((G.n + TPB - 1) / TPB, cnt, 1 + (nl + 3) / 4), dim3(TPB), 0,
-                     G.stream, x, E, G.logn, nl, (G.nmod + 3) / 4, G.key, stream, coef, logT, 2 * s, G.dev.mc, qi);
+  const dim3 grid((G.n + TPB - 1) / TPB, cnt, noise_only ? 1 : 1 + (nl + 3) / 4);
+  hipLaunchKernelGGL(enc_sk_sample_batch_kernel, grid, dim3(TPB), 0, G.stream, x, E, G.logn, nl, (G.nmod + 3) / 4,
+                     G.key, stream, coef, logT, 2 * s, G.dev.mc, qi);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -452,6 +452,30 @@ class _BatchRegulator:
         self.up = torch.zeros(count * 2 * (self.lvl - 1) * engine.n, dtype=torch.int64, device="cuda")
         torch.cuda.synchronize()
         self.timings = []
+        self._seeded_setup(4 * count)
+
+    def _seeded_setup(self, most):
+        """sym="seeded" (include/gpqhe_ext_seeded_batch.h): the public seed
+        (self.ps; `pubseed` given or fresh from os.urandom) and the staging
+        tensor for the compact c0 of up to `most` ciphertexts."""
+        import torch
+        if self.sym != "seeded":
+            assert self.pubseed is None, "pubseed goes with sym=\"seeded\""
+            return
+        self.ps = self.e.pubseed() if self.pubseed is None else self.pubseed
+        self.c0 = torch.zeros(most * (self.cw // 2), dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+
+    def _seeded(self, x_ptr, count, enc, stage=None):
+        """enc(c0_ptr, ps) -- the client: `count` compact c0 into the staging
+        tensor, the seed advanced -- then the cloud's expansion into x_ptr with
+        a copy of the seed as it was before."""
+        stage = self.c0 if stage is None else stage
+        assert stage.numel() >= count * (self.cw // 2)
+        before = type(self.ps).from_buffer_copy(self.ps)
+        enc(stage.data_ptr(), self.ps)
+        assert self.ps.stream == before.stream + count
+        self.e.expand_seeded_batch(x_ptr, stage.data_ptr(), count, self.lvl, before)
 
     def __call__(self, xhat, uhat, xr, ur):
         given, rows, width = self._zshape
@@ -473,7 +497,7 @@ class _BatchRegulator:
         e.free(self.pk)
         e.free(self.sk)
         e.free_evks(self.rk)
-        self.x = self.up = None
+        self.x = self.up = self.c0 = None
 
 
 class BatchedEncryptedRegulator(_BatchRegulator):
@@ -484,12 +508,15 @@ class BatchedEncryptedRegulator(_BatchRegulator):
     keys.  With rows=k (k >= nu: only the first nu entries of the result are
     used) the step is he_hempc_step_rows_batch, the row-folded product of the k
     leading rows, on the he_genrk_rows(k) keys.  With sym=True the encrypting
-    party uses its secret key: he_enc_sk_batch (include/gpqhe_ext_sk_batch.h).
-    Device memory comes from torch."""
+    party uses its secret key: he_enc_sk_batch (include/gpqhe_ext_sk_batch.h);
+    with sym="seeded" it ships c0 alone and the computing side regenerates c1
+    from the public seed `pubseed` (he_enc_sk_seeded_batch,
+    he_expand_seeded_batch; include/gpqhe_ext_seeded_batch.h).  Device memory
+    comes from torch."""
 
     def __init__(self, engine, problem: CstrProblem, count, g=0, seed=None, logn=12, logq=109, log_delta=50,
-                 init=True, rows=None, sym=False):
-        self.pb, self.g, self.rows, self.sym = problem, g, rows, sym
+                 init=True, rows=None, sym=False, pubseed=None):
+        self.pb, self.g, self.rows, self.sym, self.pubseed = problem, g, rows, sym, pubseed
         assert rows is None or problem.nu <= rows <= problem.slots
         s = problem.slots
         self._setup(engine, s, count, (count, count, s), problem.nu, seed, logn, logq, log_delta, init)
@@ -504,6 +531,11 @@ class BatchedEncryptedRegulator(_BatchRegulator):
 
     def _enc(self, zs):
         s = self.pb.slots
+        if self.sym == "seeded":
+            self._seeded(self.x.data_ptr(), 4 * self.count,
+                         lambda c0, ps: self.e.enc_sk_seeded_batch(c0, zs.reshape(4 * self.count, s), self.sk, s,
+                                                                   self.scale, self.lvl, ps))
+            return
         if self.sym:
             self.e.enc_sk_batch(self.x.data_ptr(), zs.reshape(4 * self.count, s), self.sk, s, self.scale, self.lvl)
             return
@@ -532,14 +564,16 @@ class PackedEncryptedRegulator(_BatchRegulator):
     loop p of every ciphertext the same, so with several ciphertexts the
     problems P apart must share their gains), or one shared pair (nmat = 1)
     when all problems are one object.  With sym=True the encryption is
-    he_enc_sk_packed_batch (include/gpqhe_ext_sk_batch.h).  __call__ is
+    he_enc_sk_packed_batch (include/gpqhe_ext_sk_batch.h), with sym="seeded"
+    he_enc_sk_seeded_packed_batch and he_expand_seeded_batch on the public seed
+    `pubseed` (include/gpqhe_ext_seeded_batch.h).  __call__ is
     BatchedEncryptedRegulator's: [len(problems)][.] arrays in, u
     [len(problems)][nu] out."""
 
     def __init__(self, engine, problems, slots_total, rows=None, seed=None, logn=12, logq=109, log_delta=50,
-                 init=True, sym=False):
+                 init=True, sym=False, pubseed=None):
         pb = problems[0]
-        self.sym = sym
+        self.sym, self.pubseed = sym, pubseed
         s = pb.slots
         self.problems, self.s, self.S = list(problems), s, slots_total
         self.rows = pb.nu if rows is None else rows
@@ -573,6 +607,12 @@ class PackedEncryptedRegulator(_BatchRegulator):
         self.e.genrk_packed(self.rk, self.sk, self.s, self.rows)
 
     def _enc(self, zs):
+        if self.sym == "seeded":
+            zz = zs.reshape(4 * self.count, self.P, self.width)
+            self._seeded(self.x.data_ptr(), 4 * self.count,
+                         lambda c0, ps: self.e.enc_sk_seeded_packed_batch(c0, zz, self.sk, self.s, self.width,
+                                                                          self.scale, self.lvl, ps))
+            return
         if self.sym:
             self.e.enc_sk_packed_batch(self.x.data_ptr(), zs.reshape(4 * self.count, self.P, self.width), self.sk,
                                        self.s, self.width, self.scale, self.lvl)
@@ -598,12 +638,13 @@ class EncryptedGainRegulator(PackedEncryptedRegulator):
     step is he_hempc_step_encgain_packed_batch on those two ciphertext sets.
     Packing, keys, encryption and decode are the parent's.  With sym=True the
     diagonals too are encrypted under the secret key
-    (he_enc_gain_sk_packed_batch)."""
+    (he_enc_gain_sk_packed_batch); with sym="seeded" they too travel as c0 and
+    the seed (he_enc_gain_sk_seeded_packed_batch, MA's m' streams first)."""
 
     def __init__(self, engine, problems, slots_total, rows=None, seed=None, logn=12, logq=109, log_delta=50,
-                 init=True, sym=False):
+                 init=True, sym=False, pubseed=None):
         import torch
-        super().__init__(engine, problems, slots_total, rows, seed, logn, logq, log_delta, init, sym)
+        super().__init__(engine, problems, slots_total, rows, seed, logn, logq, log_delta, init, sym, pubseed)
         self.rlk = engine.evk()
         engine.genrlk(self.rlk, self.sk)
         mp = 1
@@ -613,6 +654,14 @@ class EncryptedGainRegulator(PackedEncryptedRegulator):
         self.D = torch.zeros(2 * mp * self.cw, dtype=torch.int64, device="cuda")
         torch.cuda.synchronize()
         self.DA, self.DB = self.D.data_ptr(), self.D.data_ptr() + 8 * mp * self.cw
+        if sym == "seeded":
+            stage = torch.zeros(mp * (self.cw // 2), dtype=torch.int64, device="cuda")
+            torch.cuda.synchronize()
+            for dst, M in ((self.DA, self.MAz), (self.DB, self.MBz)):
+                self._seeded(dst, mp, lambda c0, ps: engine.enc_gain_sk_seeded_packed_batch(
+                    c0, M, self.sk, self.s, self.rows, self.lvl, ps, self.nmat), stage)
+            engine.sync()
+            return
         if sym:
             engine.enc_gain_sk_packed_batch(self.DA, self.MAz, self.sk, self.s, self.rows, self.lvl, self.nmat)
             engine.enc_gain_sk_packed_batch(self.DB, self.MBz, self.sk, self.s, self.rows, self.lvl, self.nmat)

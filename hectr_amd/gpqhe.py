@@ -80,6 +80,13 @@ class KStat(C.Structure):
                 ("total_us", C.c_double), ("bytes", C.c_double)]
 
 
+class PubSeed(C.Structure):
+    """gpqhe_pubseed_t (include/gpqhe_ext_seeded_batch.h): a PUBLIC ChaCha key
+    and stream; ciphertext i of a seeded call takes (key, stream + i)."""
+
+    _fields_ = [("key", C.c_uint32 * 8), ("stream", C.c_uint64)]
+
+
 P = C.POINTER
 OBJ = P(HeObject)
 VP = C.c_void_p
@@ -214,6 +221,17 @@ PRODUCT_EXT_SK_BATCH = {
     "he_enc_gain_sk_packed_batch": (None, [VP, VP, C.c_uint, C.c_uint, C.c_uint, C.c_uint, OBJ]),
 }
 
+#: include/gpqhe_ext_seeded_batch.h (part of gpqhe_ext_batch.h): the secret-key
+#: batch encryptions that ship c1 as a public seed, and the expansion on the
+#: computing side, product only, bound like PRODUCT_EXT
+PRODUCT_EXT_SEEDED_BATCH = {
+    "he_enc_sk_seeded_batch": (None, [VP, VP, C.c_size_t, C.c_uint, C.c_double, C.c_uint, OBJ, P(PubSeed)]),
+    "he_enc_sk_seeded_packed_batch": (None, [VP, VP, C.c_size_t, C.c_uint, C.c_uint, C.c_double, C.c_uint, OBJ,
+                                             P(PubSeed)]),
+    "he_enc_gain_sk_seeded_packed_batch": (None, [VP, VP, C.c_uint, C.c_uint, C.c_uint, C.c_uint, OBJ, P(PubSeed)]),
+    "he_expand_seeded_batch": (None, [VP, VP, C.c_size_t, C.c_uint, P(PubSeed)]),
+}
+
 
 def _cplx(z) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(z, dtype=np.complex128))
@@ -238,7 +256,7 @@ class Engine:
         for sym, (res, args) in {**PRODUCT_EXT, **PRODUCT_EXT_BATCH, **PRODUCT_EXT_IO_BATCH,
                                  **PRODUCT_EXT_STEP_BATCH, **PRODUCT_EXT_ROWS_BATCH,
                                  **PRODUCT_EXT_PACKED_BATCH, **PRODUCT_EXT_ENCGAIN_BATCH,
-                                 **PRODUCT_EXT_SK_BATCH}.items():
+                                 **PRODUCT_EXT_SK_BATCH, **PRODUCT_EXT_SEEDED_BATCH}.items():
             if hasattr(self.lib, sym):  # not the oracle, nor an older library under GPQHE_LIB
                 f = getattr(self.lib, sym)
                 f.restype = res
@@ -533,6 +551,48 @@ class Engine:
         M = _cplx(M)
         assert M.size >= nmat * rows * s
         f(d_ptr, M.ctypes.data, s, rows, nmat, nlimbs, C.byref(sk))
+
+    @staticmethod
+    def pubseed(key=None, stream=0) -> PubSeed:
+        """A public seed for the seeded calls: key 32 bytes (None: from
+        os.urandom), stream its first stream number.  The encrypting calls
+        advance it; a (key, stream) pair must never serve two ciphertexts
+        under one secret key."""
+        key = os.urandom(32) if key is None else bytes(key)
+        assert len(key) == 32 and 0 <= stream < 1 << 64
+        ps = PubSeed(stream=stream)
+        ps.key[:] = np.frombuffer(key, dtype="<u4").tolist()
+        return ps
+
+    def enc_sk_seeded_batch(self, c0_ptr, zs, sk, slots, scale, nlimbs, ps):
+        """enc_sk_batch that ships c1 as the seed: the compact c0 of the rows of
+        zs [count][slots] into device memory c0_ptr [count][nlimbs][n]; ps
+        advances by count (include/gpqhe_ext_seeded_batch.h)."""
+        f = self._ext("he_enc_sk_seeded_batch")
+        zs = _cplx(zs).reshape(-1, slots)
+        f(c0_ptr, zs.ctypes.data, zs.shape[0], slots, scale, nlimbs, C.byref(sk), C.byref(ps))
+
+    def enc_sk_seeded_packed_batch(self, c0_ptr, zs, sk, s, width, scale, nlimbs, ps):
+        """enc_sk_packed_batch likewise: zs [count][slots / s][width] into device
+        memory c0_ptr [count][nlimbs][n] (include/gpqhe_ext_seeded_batch.h)."""
+        f = self._ext("he_enc_sk_seeded_packed_batch")
+        zs = _cplx(zs).reshape(-1, self.slots // s, width)
+        f(c0_ptr, zs.ctypes.data, zs.shape[0], s, width, scale, nlimbs, C.byref(sk), C.byref(ps))
+
+    def enc_gain_sk_seeded_packed_batch(self, d0_ptr, M, sk, s, rows, nlimbs, ps, nmat=1):
+        """enc_gain_sk_packed_batch likewise: the m' diagonals' c0 into device
+        memory d0_ptr [m'][nlimbs][n]; ps advances by m'
+        (include/gpqhe_ext_seeded_batch.h)."""
+        f = self._ext("he_enc_gain_sk_seeded_packed_batch")
+        M = _cplx(M)
+        assert M.size >= nmat * rows * s
+        f(d0_ptr, M.ctypes.data, s, rows, nmat, nlimbs, C.byref(sk), C.byref(ps))
+
+    def expand_seeded_batch(self, x_ptr, c0_ptr, count, nlimbs, ps):
+        """The computing side: c0_ptr [count][nlimbs][n] and the seed AS IT WAS
+        BEFORE the encrypting call -> x_ptr [count][2][nlimbs][n], device memory;
+        needs no key (include/gpqhe_ext_seeded_batch.h)."""
+        self._ext("he_expand_seeded_batch")(x_ptr, c0_ptr, count, nlimbs, C.byref(ps))
 
     def dec_dcd_batch(self, y_ptr, count, nlimbs, scale, sk, slots):
         """he_dec + he_dcd_ex of `count` ciphertexts in device memory y_ptr

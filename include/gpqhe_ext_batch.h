@@ -41,5 +41,7 @@ void he_gemv_bsgs_batch(uint64_t *y, const gpqhe_complex_t M[], const uint64_t *
 #include "gpqhe_ext_encgain_batch.h"
 /* the encrypting end under the secret key: one transform per ciphertext */
 #include "gpqhe_ext_sk_batch.h"
+/* ... with c1 shipped as a public seed: half the ciphertext */
+#include "gpqhe_ext_seeded_batch.h"
 
 #endif /* GPQHE_EXT_BATCH_H */
