@@ -411,6 +411,69 @@ def noise_terms(params, op, **kw):
              Each step j != 0 adds one more rot noise; all of it is divided
              by q_top, and he_rescale adds md(1).  Against
              sum_{j,i} pt_{j,i}(X^(5^jg)) * dec(x)(X^(5^(jg+i))) / q_top.
+    step     up = moddown(uhat) - y, y the gemv_bsgs of TWO operands with shared
+             giants: u_j = sum_i pt^A_{j,i} * a_i + pt^B_{j,i} * b_i, a_i =
+             rot_i(xa), b_i = rot_i(xb) (kw g; kw steps: {j: {i != 0: [the
+             plaintexts of every operand that has diagonal jg + i]}}).  The
+             subtractions before and after and he_moddown add nothing, so the
+             noise is -noise(y): the gemv_bsgs terms with, per giant step,
+             S_j = sum over both operands, and one change: a_i and b_i are
+             rotated by the SAME key, so in E^a_i = sum_j d~^a_j(X^g) * e_{i,j}
+             and E^b_i the key errors are shared.  The digits of the two
+             ciphertexts are independent words, so their fluctuations add in
+             variance, V n (||pt^A||^2 + ||pt^B||^2) Var d~, but their common
+             mean mu_j adds before it is squared: V mu^2 ||(pt^A + pt^B) *
+             1(X^g)||^2 (ks_shared).  r0 and r1 of the two ModDowns are
+             independent; their means go into the walk and the bias through S_j.
+    rows, packed   y = F(rescale(u)), u = sum_r sum_o pt_{r,o} * rot_r(x_o) over
+             the baby rotations r (kw babies: {r != 0: [plaintexts]}; rows: r = i,
+             packed: r = i P), F = prod_t (1 + sigma_{r_t}) the fold
+             u <- u + rot(u, r_t) (kw folds: r_0, r_1, ..: m', 2m', .. times P).
+             With R = -(K/2) - (K/2) 1 * s + rho one rotation's noise (rho of
+             mean 0: E / P and the fluctuations of r0, r1 * s; rot above),
+               u1 = rescale(u) carries -(b1 + w1 * s) + rho1,
+               b1 = w1 = (K/2) T(S) / q_top + 1/2,   S = sum of all pt_{r,o},
+               Var rho1 = [sum_r ks_shared + ||pt||^2 (K/12)(1 + n/2)] / q_top^2
+                          + (1/12)(1 + n/2)           (the rescale is md(1)),
+             and fold step t adds R_t (at the level below) AFTER doubling what
+             is there: u_{t+1} = u_t + sigma_{r_t}(u_t) + R_t.  Unrolled,
+               noise(y) = sum_{g in G_0} sigma_g(u1's) + sum_t sum_{g in G_{t+1}} sigma_g(R_t),
+             G_t the 2^(T-t) rotations that are sums of subsets of r_t .. r_{T-1}:
+             the baby term appears under all 2^T images, the noise of fold step
+             t under 2^(T-1-t).  An automorphism permutes coefficients (with
+             signs), so for a typical output coefficient the images are
+             different coefficients and the variance doubles per fold step --
+             but coefficient 0 (and every k with k (5^r - 1) = 0 mod 2n) is
+             fixed by all of them, where the images add coherently.  A ceiling
+             on the max-norm has to hold there, so:
+               walk, bias  every term -(b + w * s) of every image is a fixed
+                        polynomial times the one secret: variance and bias per
+                        output coefficient are exact (images(): the
+                        cross-correlations of the w at the index differences,
+                        as for gemv_bsgs), the largest is taken;
+               rest     the rho of the images of one polynomial are taken as
+                        fully coherent (standard deviations added: |G_0|
+                        sqrt(Var rho1) + sum_t |G_{t+1}| sqrt(Var rho_t)),
+                        which is what coefficient 0 sees; uncorrelated with
+                        the walk, so the variances of the two add.
+             This is why the ceiling of 2^T images is about sqrt(2^T) above a
+             typical coefficient's 6 sigma; T = 3 in the audited shapes.
+             Against F(sum pt_{r,o} * dec(x_o)(X^(5^r))) / q_top.
+    encgain  the same with the gains encrypted: the 2 m' pairs (rot_r(x_o),
+             D_{r,o}) are tensored and summed, X0 + X1 s + X2 s^2 =
+             sum dec(rot_r(x_o)) dec(D_{r,o}) exactly, so the babies' noise is
+             sum_r R_r * dec(D_{r,o}): the baby terms above with the exact
+             decryption of the gain ciphertext (diagonal at scale q_top plus
+             its fresh noise) in the place of the plaintext (dense, so the
+             products are taken by FFT).  The division is not one rescale but
+             two: (X0, X1) by he_rescale, md(1), and the quadratic term by one
+             relinearisation with the fused ModDown, ks(P q_top) + md(K + 1)
+             (mul_rescale above, of (0, X2) and (0, 1): no other term).  So
+               b1 = w1 = (K/2) T(S) / q_top + (K + 2)/2,
+               Var rho1 = [babies] / q_top^2 + ks(P q_top)
+                          + ((K + 1)/12 + 1/12)(1 + n/2),
+             then the fold as above.  Against
+             F(sum dec(D_{r,o}) * dec(x_o)(X^(5^r))) / q_top.
     """
     n, primes, L, alpha, lvl = params["n"], params["primes"], params["L"], params["alpha"], params["lvl"]
     K = len(primes) - L
@@ -425,10 +488,11 @@ def noise_terms(params, op, **kw):
         mean, sq = _uniform_sum_moments(k)
         return Term(-mean, k / 12.0 + n * TERNARY_DENSITY * sq)
 
-    def ks(D):
+    def ks(D, level=None):
+        level = lvl if level is None else level
         tot = 0.0
-        for lo in range(0, lvl, alpha):
-            hi = min(lo + alpha, lvl)
+        for lo in range(0, level, alpha):
+            hi = min(lo + alpha, level)
             Q = 1
             for f in primes[lo:hi]:
                 Q *= f
@@ -468,42 +532,127 @@ def noise_terms(params, op, **kw):
             tot += (Q / D) ** 2 * (n * norm2 * a / 12.0 + (a / 2.0) ** 2 * mean2)
         return V * tot
 
-    if op == "gemv":
-        D = P * primes[lvl - 1]
-        return Term(0, sum(ks_times(pt, D, d) for d, pt in kw["diags"].items())) + md(K + 1)
-    if op == "gemv_bsgs":
-        qtop, g = primes[lvl - 1], kw["g"]
-        mean, sq = _uniform_sum_moments(K)
-        walks, rest_sigma, bias = {}, 0.0, np.zeros(n)
+    def conv(a, b):
+        """a * b in R[X]/(X^n + 1) for float vectors (one FFT of length 2 n)."""
+        c = np.fft.irfft(np.fft.rfft(a, 2 * n) * np.fft.rfft(b, 2 * n), 2 * n)
+        return c[:n] - c[n:]
+
+    def ks_shared(pts, D, r, level=None):
+        """ks_times for operands rotated by the SAME key (rotation r): the
+        variance per coefficient of (sum_o pt_o * d~_{o,j}(X^(5^r))) * e_j / D.
+        The operands' digits are independent ciphertext words, so the
+        fluctuations of the d~_{o,j} add in variance (n ||pt_o||^2 Var d~ each),
+        but they have one mean mu_j, whose terms add before they are squared:
+        mu^2 ||(sum_o pt_o) * 1(X^g)||^2."""
+        level = lvl if level is None else level
+        pts = [np.asarray(pt, dtype=float) for pt in pts]
+        norm2 = float(sum(np.dot(pt, pt) for pt in pts))
+        signs = np.array(automorphism_int([1] * n, pow(5, r, 2 * n)), dtype=float)
+        mean2 = float(np.sum(conv(sum(pts), signs) ** 2))
+        tot = 0.0
+        for lo in range(0, level, alpha):
+            a = min(lo + alpha, level) - lo
+            Q = 1
+            for f in primes[lo:lo + a]:
+                Q *= f
+            tot += (Q / D) ** 2 * (n * norm2 * a / 12.0 + (a / 2.0) ** 2 * mean2)
+        return V * tot
+
+    def images(items):
+        """(largest |bias|, largest walk variance / E s^2) over the output
+        coefficients of sum_m sigma_m(b_m + w_m * s), sigma_m the automorphism
+        X -> X^(5^r_m), for items (r_m, b_m, w_m) of fixed real polynomials.
+        Coefficient k of image m reads coefficient k 5^(-r_m) mod 2n of the
+        antiperiodic extension; the sum is linear in the one secret, so its
+        variance per output coefficient is exact: (E s^2) || sum_m w_m^(k) ||^2,
+        whose cross terms are negacyclic cross-correlations of the w_m at the
+        difference of those indices."""
         ext = lambda v: np.concatenate([v, -v])  # one period of the antiperiodic extension
-        at = {j: (np.arange(n) * pow(pow(5, j * g, 2 * n), -1, 2 * n)) % (2 * n) for j in kw["steps"]}
-        for j, pts in kw["steps"].items():  # giant step j: {baby i != 0: coefficients of pt_{j,i}}
+        full = lambda v: np.full(n, float(v)) if np.ndim(v) == 0 else np.asarray(v, dtype=float)
+        items = [(r, full(b), full(w)) for r, b, w in items]
+        at = [(np.arange(n) * pow(pow(5, r, 2 * n), -1, 2 * n)) % (2 * n) for r, _, _ in items]
+        fw = [np.fft.fft(ext(w)) for _, _, w in items]
+        bias, var = np.zeros(n), np.zeros(n)
+        for a, (_, b, w) in enumerate(items):
+            bias += ext(b)[at[a]]
+            var += float(np.sum(w * w))
+            for c in range(a + 1, len(items)):
+                rho = np.real(np.fft.ifft(np.conj(fw[a]) * fw[c])) / 2.0
+                var += 2.0 * rho[(at[c] - at[a]) % (2 * n)]
+        return float(np.abs(bias).max()), float(var.max())
+
+    def baby_terms(babies, level_D=P):
+        """For u = sum over rotations r != 0 and operands o of pt_{r,o} * rot_r(x_o)
+        (babies: {r: [pt_{r,o}]}): (T(S), variance of the rest).  Every rotated
+        operand carries N = E / P - r0 - r1 * s (rot above), so u's noise is
+        sum pt * N: the means K/2 of the r0 and r1 give (K/2) T(S) and
+        (K/2) T(S) * s, S the sum of all the plaintexts, T(S) = S * 1 (partial
+        sums: T_k = 2 sum_{i<=k} S_i - sum_i S_i); the rest is the key-switch
+        term of every rotation (ks_shared: one key per rotation, shared by the
+        operands), r0 about its mean (K/12) ||pt||^2 and (r1 about its mean) * s,
+        (1/2) n (K/12) ||pt||^2, of every plaintext."""
+        S, var = np.zeros(n), 0.0
+        for r, pts in babies.items():
+            pts = [np.asarray(pt, dtype=float) for pt in pts]
+            norm2 = float(sum(np.dot(pt, pt) for pt in pts))
+            S = S + sum(pts)
+            var += ks_shared(pts, level_D, r) + norm2 * (K / 12.0) * (1.0 + TERNARY_DENSITY * n)
+        return 2.0 * np.cumsum(S) - S.sum(), var
+
+    def bsgs(steps, g):
+        """steps: {giant step j: {baby i != 0: [coefficients of pt_{j,i} of every operand]}}"""
+        qtop = primes[lvl - 1]
+        mean, sq = _uniform_sum_moments(K)
+        items, rest_sigma = [], 0.0
+        for j, pts in steps.items():
             if not pts:
                 continue
-            norm2 = float(sum(sum(c * c for c in pt) for pt in pts.values()))
-            T = times([sum(col) for col in zip(*pts.values())], ones)  # T_k(S_j)
-            var = sum(ks_times(pt, P, i) for i, pt in pts.items())   # E_i / P, independent keys
-            var += norm2 * K / 12.0                                  # r0_i about its mean
-            var += TERNARY_DENSITY * n * norm2 * K / 12.0            # (r1_i about its mean) * s
+            T, var = baby_terms(pts)
             rest_sigma += math.sqrt(var)
-            walks[j] = mean * T                                      # the means of the r1_i: (K/2) T(S_j) * s
-            bias += ext(mean * T)[at[j]]                             # the means of the r0_i, after the giant rotation
+            # the means of the r0_i and of the r1_i, after the giant rotation:
+            # (K/2) T(S_j) and (K/2) T(S_j) * s
+            items.append((j * g, mean * T, mean * T))
         # the walks of all giant steps are linear in the one secret: exact
         # variance per output coefficient k, (1/2) || sum_j w_j^(k) ||^2
-        var_walk = np.full(n, sum(float(np.sum(w * w)) for w in walks.values()))
-        js = sorted(walks)
-        for a_i, ja in enumerate(js):
-            fa = np.conj(np.fft.fft(ext(walks[ja])))
-            for jb in js[a_i + 1:]:
-                rho = np.real(np.fft.ifft(fa * np.fft.fft(ext(walks[jb])))) / 2.0
-                var_walk += 2.0 * rho[(at[jb] - at[ja]) % (2 * n)]
-        giants = sum(1 for j in kw["steps"] if j)
+        bias, var_walk = images(items) if items else (0.0, 0.0)
+        giants = sum(1 for j in steps if j)
         giant = ks(P) + md(K)
         rest_sigma += giants * math.sqrt(giant.var)
         # the walk (the secret times fixed polynomials) is uncorrelated with the
         # rest (zero-mean fluctuations and key errors): variances add
-        var = TERNARY_DENSITY * float(var_walk.max()) + rest_sigma ** 2
-        return Term((float(np.abs(bias).max()) + giants * abs(giant.bias)) / qtop, var / qtop ** 2) + md(1)
+        var = TERNARY_DENSITY * var_walk + rest_sigma ** 2
+        return Term((bias + giants * abs(giant.bias)) / qtop, var / qtop ** 2) + md(1)
+
+    if op == "gemv":
+        D = P * primes[lvl - 1]
+        return Term(0, sum(ks_times(pt, D, d) for d, pt in kw["diags"].items())) + md(K + 1)
+    if op == "gemv_bsgs":
+        return bsgs({j: {i: [pt] for i, pt in pts.items()} for j, pts in kw["steps"].items()}, kw["g"])
+    if op == "step":
+        return bsgs(kw["steps"], kw["g"])
+    if op in ("rows", "packed", "encgain"):
+        qtop = primes[lvl - 1]
+        mean = K / 2.0
+        T, var1 = baby_terms(kw["babies"])
+        var1 /= float(qtop) ** 2
+        # the division: he_rescale, or for the encrypted gains one relinearisation
+        # of X2 with the fused ModDown by P q_top beside he_rescale of (X0, X1)
+        drop = (K + 2) if op == "encgain" else 1
+        if op == "encgain":
+            var1 += ks(P * qtop).var
+        first = mean * T / qtop + drop / 2.0
+        var1 += (drop / 12.0) * (1.0 + TERNARY_DENSITY * n)
+        folds = list(kw["folds"])
+        sums = lambda rs: [sum(r for b, r in enumerate(rs) if m >> b & 1) for m in range(1 << len(rs))]
+        items = [(r, first, first) for r in sums(folds)]
+        rest_sigma = len(items) * math.sqrt(var1)
+        var_rot = ks(P, lvl - 1).var + (K / 12.0) * (1.0 + TERNARY_DENSITY * n)
+        for t in range(len(folds)):
+            later = sums(folds[t + 1:])
+            items += [(r, mean, mean) for r in later]
+            rest_sigma += len(later) * math.sqrt(var_rot)
+        bias, var_walk = images(items)
+        return Term(bias, TERNARY_DENSITY * var_walk + rest_sigma ** 2)
     if op == "enc_pk":
         return fresh_pk
     if op == "enc_sk":

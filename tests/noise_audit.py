@@ -7,6 +7,12 @@ The only engine code they lean on is he_export and the CPU engine's
 poly_ntt_batch / poly_intt_batch on host arrays (pinned to the definition by
 test_oracle_model.py and test_extremes_cpu.py); the product's objects are
 transformed by the CPU engine too (use_host_transforms).
+
+The batch entry points return raw word arrays, not objects, so the audits of
+one ciphertext come in an array form (exact_decrypt_words, audit_enc_pk_words,
+audit_enc_sk_words, audit_enc_sk_seeded_words) that the object forms call.
+measure_step runs one step family -- the reference composition on the oracle,
+the batch entry point on the product -- and returns its exact noise.
 """
 import ctypes
 
@@ -183,20 +189,23 @@ def audit_evk(engine, st, evk, s, s_ntt, galois, idx=None, a_limbs=None):
     return errs
 
 
-def audit_enc_pk(engine, st, ct, pt, pk, idx=None):
-    """(v, e0, e1) of one he_enc_pk against three fresh streams: with the
-    model's v, INTT(c1 - v a) and INTT(c0 - v b - m) must be the model's e1 and
-    e0.  v itself is the model's: that c1 - v a is small at all (one integer of
-    CBD size on every limb) shows it is the v the engine drew, a uniform a
-    leaving no second small solution.  Returns (v, e0, e1)."""
+def audit_enc_pk_words(engine, st, words, m_ntt, pk_words, idx=None):
+    """(v, e0, e1) of one public-key encryption, words [2][nl][n], of the
+    plaintext words m_ntt [nl][n] under the exported public key pk_words,
+    against three fresh streams: with the model's v, INTT(c1 - v a) and
+    INTT(c0 - v b - m) must be the model's e1 and e0.  v itself is the model's:
+    that c1 - v a is small at all (one integer of CBD size on every limb) shows
+    it is the v the engine drew, a uniform a leaving no second small solution.
+    Returns (v, e0, e1)."""
     n = engine.n
-    lvl = ct.nlimbs
+    c, p, m = (np.asarray(x, dtype=np.uint64) for x in (words, pk_words, m_ntt))
+    lvl = c.shape[1]
+    assert c.shape == (2, lvl, n) and m.shape == (lvl, n)
     primes = engine.primes[:lvl]
     idx = np.arange(n) if idx is None else idx
     v = R.sample_ternary(st.key, st.take(), n)
     s0, s1 = st.take(), st.take()
     v_ntt = ntt(engine, lift(v, primes))
-    c, p, m = engine.export(ct), engine.export(pk), engine.export(pt)[0]
     r0 = np.stack([submod(submod(c[0, i], mulmod(v_ntt[i], p[0, i], q), q), m[i], q) for i, q in enumerate(primes)])
     r1 = np.stack([submod(c[1, i], mulmod(v_ntt[i], p[1, i], q), q) for i, q in enumerate(primes)])
     e0 = small_of(intt(engine, r0), primes, "e0")
@@ -204,6 +213,79 @@ def audit_enc_pk(engine, st, ct, pt, pk, idx=None):
     assert np.array_equal(e0[idx], R.sample_cbd(st.key, s0, n, idx)), "e0 is not the model's CBD sample"
     assert np.array_equal(e1[idx], R.sample_cbd(st.key, s1, n, idx)), "e1 is not the model's CBD sample"
     return v, e0, e1
+
+
+def audit_enc_pk(engine, st, ct, pt, pk, idx=None):
+    """audit_enc_pk_words on the exported objects of one he_enc_pk."""
+    return audit_enc_pk_words(engine, st, engine.export(ct), engine.export(pt)[0], engine.export(pk), idx)
+
+
+def sk_error_of(engine, c0, a, m_ntt, s_ntt, what="e"):
+    """The small polynomial INTT(c0 + a s - m) of a secret-key encryption: one
+    integer on every limb (checked), |e| <= 21."""
+    lvl = np.asarray(c0).shape[0]
+    primes = engine.primes[:lvl]
+    r = np.stack([submod(addmod(c0[i], mulmod(a[i], s_ntt[i], q), q), m_ntt[i], q) for i, q in enumerate(primes)])
+    e = small_of(intt(engine, r), primes, what)
+    assert np.abs(e).max() <= R.CBD_ETA, f"{what}: |e| reaches {np.abs(e).max()}"
+    return e
+
+
+def audit_enc_sk_words(engine, st, words, m_ntt, s_ntt, idx=None):
+    """(a, e) of one secret-key encryption, words [2][nl][n], of the plaintext
+    words m_ntt [nl][n] under the secret s_ntt, against two fresh streams: every
+    limb of c1 is the model's uniform sample of the first, and
+    INTT(c0 + c1 s - m) is one small integer on every limb, the model's CBD
+    sample of the second, |e| <= 21.  Returns (c1 [nl][n], e)."""
+    n = engine.n
+    c = np.asarray(words, dtype=np.uint64)
+    lvl = c.shape[1]
+    assert c.shape == (2, lvl, n) and np.asarray(m_ntt).shape == (lvl, n)
+    idx = np.arange(n) if idx is None else idx
+    sa, se = st.take(), st.take()
+    for m in range(lvl):
+        want = R.sample_uniform(st.key, sa, n, m, engine.primes[m], engine.L + engine.K, idx)
+        assert np.array_equal(c[1, m][idx], want), f"c1 limb {m} is not the model's uniform sample of stream {sa}"
+    e = sk_error_of(engine, c[0], c[1], m_ntt, s_ntt)
+    assert np.array_equal(e[idx], R.sample_cbd(st.key, se, n, idx)), f"e is not the model's CBD sample of stream {se}"
+    return c[1], e
+
+
+def audit_enc_sk_seeded_words(engine, st, c0, m_ntt, s_ntt, pub_key, pub_stream, idx=None):
+    """(a, e) of one seeded secret-key encryption, c0 [nl][n]: a is the model's
+    uniform sample under the PUBLIC key words pub_key and stream pub_stream
+    (nothing of the engine's enters it); the private counter advances by two,
+    the first of which is skipped, and INTT(c0 + a s - m) is the model's CBD
+    sample of the second.  Returns (a [nl][n], e)."""
+    n = engine.n
+    c0 = np.asarray(c0, dtype=np.uint64)
+    lvl = c0.shape[0]
+    assert c0.shape == (lvl, n) and np.asarray(m_ntt).shape == (lvl, n)
+    idx = np.arange(n) if idx is None else idx
+    a = np.stack([R.sample_uniform(pub_key, pub_stream, n, m, engine.primes[m], engine.L + engine.K)
+                  for m in range(lvl)])
+    st.take()  # the stream he_enc_sk would draw c1 from: skipped
+    se = st.take()
+    e = sk_error_of(engine, c0, a, m_ntt, s_ntt)
+    assert np.array_equal(e[idx], R.sample_cbd(st.key, se, n, idx)), f"e is not the model's CBD sample of stream {se}"
+    return a, e
+
+
+def audit_enc_sk(engine, st, ct, pt, sk, idx=None):
+    """audit_enc_sk_words on the exported objects of one he_enc_sk."""
+    lvl = ct.nlimbs
+    return audit_enc_sk_words(engine, st, engine.export(ct), engine.export(pt)[0][:lvl], engine.export(sk)[0][:lvl], idx)
+
+
+def encoded_words(engine, z, slots, scale, nlimbs):
+    """The plaintext words [nlimbs][n] of z: the CPU engine's he_ecd_ex,
+    exported (the engines' common encoding, pinned by test_noise_cpu.py)."""
+    host = _host(engine)
+    pt = host.pt()
+    host.ecd_ex(pt, z, slots, scale, nlimbs)
+    m = host.export(pt)[0][:nlimbs].copy()
+    host.free(pt)
+    return m
 
 
 def pairwise_distinct(polys):
@@ -228,16 +310,22 @@ def crt_centred(res, primes):
     return np.where(x > Q // 2, x - Q, x)
 
 
-def exact_decrypt(engine, ct, sk):
-    """Centred Python-integer coefficients of c0 + c1 s modulo Q_level: the
-    product per limb on the exported words, the engine's inverse transform
+def exact_decrypt_words(engine, words, s_ntt):
+    """Centred Python-integer coefficients of c0 + c1 s modulo Q_level for the
+    ciphertext words [2][nl][n] and the secret's words s_ntt (its first nl
+    limbs are read): the product per limb, the engine's inverse transform
     (pinned separately), then an exact centred CRT."""
-    c = engine.export(ct)
-    lvl = ct.nlimbs
-    s = engine.export(sk)[0]
+    c = np.asarray(words, dtype=np.uint64)
+    lvl = c.shape[1]
+    assert c.shape == (2, lvl, engine.n)
     primes = engine.primes[:lvl]
-    m = np.stack([addmod(c[0, i], mulmod(c[1, i], s[i], q), q) for i, q in enumerate(primes)])
+    m = np.stack([addmod(c[0, i], mulmod(c[1, i], s_ntt[i], q), q) for i, q in enumerate(primes)])
     return crt_centred(intt(engine, m), primes)
+
+
+def exact_decrypt(engine, ct, sk):
+    """exact_decrypt_words of an exported ciphertext and secret key."""
+    return exact_decrypt_words(engine, engine.export(ct), engine.export(sk)[0])
 
 
 def exact_plain(engine, pt):
@@ -474,3 +562,205 @@ def measure_bsgs(e, seed, diags, g):
 
 def bsgs_ceiling(e, extra):
     return M.noise_ceilings(model_params(e), "gemv_bsgs", **extra) + GEMV_SLACK
+
+
+# --------------------------------------------------------------------------- the step products
+#: the step families: the reference composition (on the oracle) and the
+#: product's entry point that it defines
+STEP_KINDS = ("step", "rows", "packed", "encgain")
+#: slack of the step comparisons: the expected message is built from exact
+#: integers throughout (exact decryptions, the engine's own plaintexts), so the
+#: only allowance is one unit for the rounding of the comparison itself
+STEP_SLACK = 1
+
+
+def automorphism_obj(a, g):
+    """a(X) -> a(X^g) on an object (Python integer) coefficient vector."""
+    a = np.asarray(a, dtype=object)
+    n = a.size
+    e = (np.arange(n, dtype=np.int64) * int(g)) % (2 * n)
+    out = np.zeros(n, dtype=object)
+    out[e % n] = np.where(e < n, a, -a)
+    return out
+
+
+def plain_coeffs(engine, z, slots, scale, nlimbs):
+    """The exact centred coefficients of the engine's encoding of z."""
+    return crt_centred(intt(engine, encoded_words(engine, z, slots, scale, nlimbs)), engine.primes[:nlimbs])
+
+
+def _device(words):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(words, dtype=np.uint64).ravel().view(np.int64)).cuda()
+
+
+def _words_out(engine, count, nl):
+    import torch
+    t = torch.zeros(count * 2 * nl * engine.n, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    return t
+
+
+def _read(engine, t, count, nl):
+    engine.sync()
+    return t.cpu().numpy().view(np.uint64).reshape(count, 2, nl, engine.n)
+
+
+def step_matrices(kind, S, s, rows, diags):
+    """The gains of a step case, the same for every seed: entries uniform in
+    [-2, 2].  step: two s x s matrices with the non-zero diagonals diags =
+    (of Ma, of Mb); the other kinds: [nmat][rows][s] leading rows, nmat = 1
+    for rows and P = S / s (every loop its own) for packed and encgain."""
+    rng = np.random.default_rng(0)
+    if kind == "step":
+        return matrix_with_diagonals(s, diags[0], rng), matrix_with_diagonals(s, diags[1], rng)
+    nmat = 1 if kind == "rows" else S // s
+    return rng.uniform(-2, 2, (nmat, rows, s)), rng.uniform(-2, 2, (nmat, rows, s))
+
+
+def measure_step(e, seed, kind, s=None, rows=None, g=0, diags=None, count=1, sym=False):
+    """([(max |noise|, mean noise) per ciphertext], model arguments) of one
+    step family on engine e (context of S = e.slots slots initialised) after
+    gpqhe_set_seed(seed): on the oracle the reference composition of
+    tests/{step,rows,packed,encgain}_ref.py, on the product its batch entry
+    point over `count` ciphertexts in device memory.
+
+    up = moddown(uhat) - W(xhat - xr, uhat - ur); the expected message is, in
+    exact integers,
+        dec(uhat) - F(sum_r pt^A_r * xd(X^(5^r)) + pt^B_r * ud(X^(5^r))) / q_top
+    with xd = dec(xhat) - dec(xr), ud = dec(uhat) - dec(ur) from the exact
+    decryptions of the four inputs, pt_r the engine's own plaintext of the
+    diagonal (for encgain: the exact decryption of the gain ciphertext), and F
+    the giant rotations of the BSGS (step) or the row fold prod (1 + sigma_r).
+    So the noise is what the key switches, ModDowns and rescales add.
+    sym: the encgain gains encrypted under the secret key."""
+    import bsgs_ref as B
+    from tests import encgain_ref, packed_ref, rows_ref, sk_ref, step_ref
+    assert kind in STEP_KINDS
+    product = e.name != "oracle"
+    n, L, S = e.n, e.L, e.slots
+    s = s or S
+    P = S // s
+    if kind in ("step", "rows"):
+        assert s == S
+    qtop = int(e.primes[L - 1])
+    e.set_seed(seed)
+    pk, sk = e.pk(), e.sk()
+    e.keypair(pk, sk)
+    rlk = None
+    if kind == "step":
+        g = g or B.default_g(S)
+        rk = B.bsgs_keys(e, sk, g)
+    elif kind == "rows":
+        rk = rows_ref.rows_keys(e, sk, rows)
+    else:
+        rk = packed_ref.packed_keys(e, sk, s, rows)
+    if kind == "encgain":
+        rlk = e.evk()
+        e.genrlk(rlk, sk)
+    Ma, Mb = step_matrices(kind, S, s, rows, diags)
+    nmat = 1 if kind == "rows" else P
+    s_ntt = e.export(sk)[0]
+    # the gains: {rotation r: (plaintext of Ma, of Mb)} and the images F sums over
+    gains, DA, DB = {}, None, None
+    if kind == "step":
+        da, db = B.diagonals(Ma, S), B.diagonals(Mb, S)
+        for d in sorted(set(da) | set(db)):
+            j = d // g
+            gains[d] = tuple(plain_coeffs(e, np.roll(dd[d], j * g), S, float(qtop), L) if d in dd else None
+                             for dd in (da, db))
+        folds = []
+    else:
+        mp = rows_ref.pow2(rows)
+        if kind == "rows":
+            da, db = rows_ref.extended_diagonals(Ma, S, rows), rows_ref.extended_diagonals(Mb, S, rows)
+        else:
+            da, db = packed_ref.packed_diagonals(Ma, S, s, rows, nmat), packed_ref.packed_diagonals(Mb, S, s, rows, nmat)
+        if kind == "encgain":
+            if sym:
+                DA = sk_ref.enc_gain_sk_compose(e, Ma, sk, s, rows, nmat, L)
+                DB = sk_ref.enc_gain_sk_compose(e, Mb, sk, s, rows, nmat, L)
+            else:
+                DA = encgain_ref.enc_gain_compose(e, Ma, pk, s, rows, nmat, L)
+                DB = encgain_ref.enc_gain_compose(e, Mb, pk, s, rows, nmat, L)
+            for i in range(mp):
+                gains[i * P] = (exact_decrypt(e, DA[i], sk), exact_decrypt(e, DB[i], sk))
+        else:
+            for i in sorted(set(da) | set(db)):
+                gains[i * P] = tuple(plain_coeffs(e, dd[i], S, float(qtop), L) if i in dd else None for dd in (da, db))
+        folds = []
+        r = mp
+        while r < s:
+            folds.append(r * P)
+            r *= 2
+    rng = np.random.default_rng(seed)
+    zs = rng.uniform(-1, 1, (count, 4, S)) + 1j * rng.uniform(-1, 1, (count, 4, S))
+    cts = [[e.encrypt(zs[c, b], pk, S, SCALE, L) for b in range(4)] for c in range(count)]
+    words = np.stack([[e.export(x) for x in blk] for blk in cts])  # [count][4][2][L][n]
+    if product:
+        din = _device(np.ascontiguousarray(words.transpose(1, 0, 2, 3, 4)))  # blocks xhat, xr, uhat, ur
+        ptr = [din.data_ptr() + 8 * b * count * 2 * L * n for b in range(4)]
+        dout = _words_out(e, count, L - 1)
+        if kind == "step":
+            e.hempc_step_batch(dout.data_ptr(), Ma, Mb, *ptr, count, L, rk, g)
+        elif kind == "rows":
+            e.hempc_step_rows_batch(dout.data_ptr(), Ma, Mb, *ptr, count, L, rk, rows)
+        elif kind == "packed":
+            e.hempc_step_packed_batch(dout.data_ptr(), Ma, Mb, *ptr, count, L, rk, s, rows, nmat)
+        else:
+            dg = _device(np.stack([e.export(x) for x in DA + DB]))
+            e.hempc_step_encgain_packed_batch(dout.data_ptr(), dg.data_ptr(), dg.data_ptr() + 8 * mp * 2 * L * n,
+                                              *ptr, count, L, rk, rlk, s, rows)
+        out = _read(e, dout, count, L - 1)
+    else:
+        out = []
+        for xhat, xr, uhat, ur in cts:
+            if kind == "step":
+                up = step_ref.step_compose(e, Ma, Mb, xhat, xr, uhat, ur, rk, g)
+            elif kind == "rows":
+                up = rows_ref.step_rows_compose(e, Ma, Mb, xhat, xr, uhat, ur, rk, rows)
+            elif kind == "packed":
+                up = packed_ref.step_packed_compose(e, Ma, Mb, xhat, xr, uhat, ur, rk, s, rows, nmat)
+            else:
+                up = encgain_ref.step_encgain_compose(e, DA, DB, xhat, xr, uhat, ur, rk, rlk, s, rows)
+            assert up.nlimbs == L - 1
+            out.append(e.export(up).copy())
+            e.free(up)
+    stats = []
+    for c in range(count):
+        dec = [exact_decrypt_words(e, words[c, b], s_ntt) for b in range(4)]
+        dx, du = dec[0] - dec[1], dec[2] - dec[3]
+        w = np.zeros(n, dtype=object)
+        for r, pts in gains.items():
+            # step: the plaintext of diagonal r = j g + i was rolled by j g and rides the giant rotation
+            giant = pow(5, r // g * g, 2 * n) if kind == "step" else 1
+            for ptv, d in zip(pts, (dx, du)):
+                if ptv is not None:
+                    w = w + negacyclic_int(automorphism_obj(ptv, giant), automorphism_obj(d, pow(5, r, 2 * n)))
+        for r in folds:
+            w = w + automorphism_obj(w, pow(5, r, 2 * n))
+        stats.append(noise_stats(exact_decrypt_words(e, out[c], s_ntt), dec[2] * qtop - w, qtop))
+    # what the model needs: the plaintexts of every rotation r != 0, per operand
+    if kind == "step":
+        steps = {}
+        for d, pts in gains.items():
+            j, i = divmod(d, g)
+            steps.setdefault(j, {})
+            if i:
+                steps[j].setdefault(i, [])
+                steps[j][i] += [np.array(p, dtype=float) for p in pts if p is not None]
+        extra = dict(steps=steps, g=g)
+    else:
+        extra = dict(babies={r: [np.array(p, dtype=float) for p in pts if p is not None]
+                             for r, pts in gains.items() if r}, folds=folds)
+    for blk in cts:
+        for x in blk:
+            e.free(x)
+    for o in [pk, sk] + ([rlk] if rlk is not None else []) + (DA or []) + (DB or []):
+        e.free(o)
+    e.free_evks(rk)
+    return stats, extra
+
+
+def step_ceiling(e, kind, extra):
+    return M.noise_ceilings(model_params(e), kind, **extra) + STEP_SLACK

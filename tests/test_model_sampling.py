@@ -2,7 +2,8 @@
 (tests/ckks_model_rng.py): ChaCha20 against openssl's keystream, the three
 sampling maps, the stream numbering (one fresh stream per sampled polynomial,
 restarted by a reseed) and the default seed.  CPU only, on the oracle; the same
-audit runs on the product in tests/test_gpu_noise_audit.py."""
+audit runs on the product in tests/test_gpu_noise_audit.py, and on its batch
+encrypting calls in tests/test_gpu_batch_audit.py."""
 import ctypes
 import json
 import os
@@ -92,8 +93,10 @@ def genrot(e, r, sk):
 
 
 def run_documented_order(e, seed):
-    """he_keypair, he_genrlk, he_genrot(1), 3 x he_enc_pk against streams
-    0, 1, 2, ...; returns the named small polynomials recovered."""
+    """he_keypair, he_genrlk, he_genrot(1), 3 x he_enc_pk, 2 x he_enc_sk and
+    one more he_enc_pk against streams 0, 1, 2, ...; returns the named small
+    polynomials recovered (the uniform c1 of the secret-key encryptions are
+    compared with each other and the public key's a here)."""
     st = A.Streams(seed)
     pk, sk = e.pk(), e.sk()
     e.keypair(pk, sk)
@@ -119,6 +122,31 @@ def run_documented_order(e, seed):
         e.free(pt)
         e.free(ct)
     assert st.next == 12 + 4 * e.info.dnum
+    # he_enc_sk: a (uniform) from the next stream, e (CBD) from the one after
+    firsts = []
+    for i in range(2):
+        z = rng.uniform(-1, 1, 8) + 1j * rng.uniform(-1, 1, 8)
+        pt, ct = e.pt(), e.ct()
+        e.ecd(pt, z)
+        e.enc_sk(ct, pt, sk)
+        t = st.next
+        a, err = A.audit_enc_sk(e, st, ct, pt, sk)
+        assert st.next == t + 2
+        small.append((f"e_sk{i}", err))
+        firsts.append((f"a_sk{i}", a))
+        e.free(pt)
+        e.free(ct)
+    assert st.next == 16 + 4 * e.info.dnum
+    # ... and a public-key encryption after them sees the next three
+    z = rng.uniform(-1, 1, 8) + 1j * rng.uniform(-1, 1, 8)
+    pt, ct = e.pt(), e.ct()
+    e.ecd(pt, z)
+    e.enc_pk(ct, pt, pk)
+    small += list(zip(("v3", "e0_3", "e1_3"), A.audit_enc_pk(e, st, ct, pt, pk)))
+    e.free(pt)
+    e.free(ct)
+    assert st.next == 19 + 4 * e.info.dnum
+    A.pairwise_distinct(firsts + [("a_pk", e.export(pk)[1])])
     for o in (pk, sk, rlk, rot):
         e.free(o)
     return small
