@@ -6,15 +6,39 @@ vector in call order; the tests compare the two engines' lists bit for bit.
 The sequences follow the reference's regulator step: encode + encrypt the
 state (src/ctr.c:461-480), he_sub x2, he_gemv x2, he_add / he_neg
 (src/hempc.c:253-266), decrypt + decode (src/ctr.c:486-490).
+
+Every sequence takes `params` (hectx_init's arguments; PARAMS_REF, HECTR's own,
+by default; PARAMS_RINGS holds the other rings the tests run) and `plain`: a
+list that receives, for every decoded vector of the result, its index there and
+the value the plaintext step gives.
 """
 import numpy as np
 
 PARAMS_REF = dict(logn=12, logq=109, slots=16, log_delta=50)  # src/ctr.c:514-518
+# The other rings of the small-N path (every sequence takes `params`): the
+# other two rungs of the fused kernels' ring-size ladders, inside the
+# speculation gate (10 <= logn <= 12); HECTR's ring with a longer chain (L = 4:
+# past the fused kernels' two-limb forms); and logn = 9, just outside the
+# gate (the oracle only: the product has no decode below n = 2^10,
+# tests/test_gpu_small_rings.py).
+PARAMS_RINGS = {
+    "n2048": dict(logn=11, logq=109, slots=16, log_delta=50),
+    "n1024": dict(logn=10, logq=109, slots=16, log_delta=50),
+    "n4096_L4": dict(logn=12, logq=209, slots=16, log_delta=50),
+    "n512": dict(logn=9, logq=109, slots=16, log_delta=50),
+}
 # he_gemv calls an "evict" step of speculative_gemvs adds.  Under a 5 MiB
 # diagonal cache: the first is queued (cache at 4.5 MiB), the second runs
 # unqueued and clears the cache at its sixth diagonal, the third and fourth are
 # queued into freed 1.5 MiB blocks, the fifth runs unqueued again.
 EVICT_EXTRAS = 5
+
+
+def note(plain, res, want):
+    """plain (a caller's list, or None) gets (index in res, plaintext value)
+    of the decoded vector just appended to res."""
+    if plain is not None:
+        plain.append((len(res) - 1, want))
 
 
 def keys(e, rot=True):
@@ -27,11 +51,11 @@ def keys(e, rot=True):
     return pk, sk, rk
 
 
-def speculative_noise(e, seed=1234, rng_seed=9):
+def speculative_noise(e, seed=1234, rng_seed=9, params=PARAMS_REF, plain=None):
     """Steps of 5 encryptions (HECTR's), then 3 (a prefix of the speculated
     streams), 6 (more than speculated), one with a live plaintext, one at a
     lower level, a reseed between steps (api.cpp SpecNoise)."""
-    e.init(**PARAMS_REF)
+    e.init(**params)
     e.set_seed(seed)
     rng = np.random.default_rng(rng_seed)
     plan = [5, 5, 3, 6, "live", "lvl1", "reseed", 5, 5]
@@ -61,19 +85,20 @@ def speculative_noise(e, seed=1234, rng_seed=9):
         e.sub(d, cts[0], cts[1])
         res += [e.export(x) for x in cts + [d]]
         res.append(e.decrypt(d, sk))  # he_dcd: the next step's noise is launched behind it
+        note(plain, res, zz[0] - zz[1])
         for x in cts + [d]:
             e.free(x)
     return res
 
 
-def queued_differences(e, seed=1234, rng_seed=31):
+def queued_differences(e, seed=1234, rng_seed=31, params=PARAMS_REF, plain=None):
     """HECTR's regulator step repeated (api.cpp ew_lazy_sub: from the second
     step on the subs stay queued and gemv_inner_kernel forms the differences
     from their operands).  Variants per step: the differences freed unread,
     read back after the gemvs, an operand of a sub overwritten after the
     gemvs, an in-place he_gemv(x, M, x), a gemv whose output is an operand of
     the queued sub, and a non-speculated step (four encryptions)."""
-    e.init(**PARAMS_REF)
+    e.init(**params)
     e.set_seed(seed)
     rng = np.random.default_rng(rng_seed)
     s = e.slots
@@ -111,17 +136,18 @@ def queued_differences(e, seed=1234, rng_seed=31):
         for x in (xd, ud, yb) + (() if kind in ("inplace", "ycts") else (ya,)):
             e.free(x)
         res.append(e.decrypt(du, sk))
+        note(plain, res, -(M1 @ (zz[0] - zz[1]) + M2 @ (zz[2] - zz[3])))
         for x in cts + [du]:
             e.free(x)
     return res
 
 
-def rekeyed_steps(e, seed=1234, rng_seed=41):
+def rekeyed_steps(e, seed=1234, rng_seed=41, params=PARAMS_REF, plain=None):
     """The regulator step with the public key changing between speculative
     steps (api.cpp SpecModup is keyed on the public key's block): two steps
     on key A; A freed and a new key C generated (its block may be A's); steps
     on C; then keys B and C alternating step by step."""
-    e.init(**PARAMS_REF)
+    e.init(**params)
     e.set_seed(seed)
     rng = np.random.default_rng(rng_seed)
     s = e.slots
@@ -152,12 +178,13 @@ def rekeyed_steps(e, seed=1234, rng_seed=41):
         for x in (xd, ud, ya, yb):
             e.free(x)
         res.append(e.decrypt(du, sk))
+        note(plain, res, -(M1 @ (zz[0] - zz[1]) + M2 @ (zz[2] - zz[3])))
         for x in cts + [du]:
             e.free(x)
     return res
 
 
-def speculative_gemvs(e, seed=1234, rng_seed=53, plan=None, taken=None):
+def speculative_gemvs(e, seed=1234, rng_seed=53, plan=None, taken=None, params=PARAMS_REF, plain=None):
     """HECTR's step with its own call order (all five encodes, all five
     encryptions, the plaintexts freed: src/ctr.c:461-480, which starts the
     early combine and, from the third step on, the speculated gemvs of the
@@ -171,7 +198,7 @@ def speculative_gemvs(e, seed=1234, rng_seed=53, plan=None, taken=None):
     with a small diagonal cache (GPQHE_DIAG_MIB) they clear it and take the
     freed blocks while the next step's speculation records point there.
     taken: a list that gets gpqhe_spec_gemv_taken() after every step."""
-    e.init(**PARAMS_REF)
+    e.init(**params)
     e.set_seed(seed)
     rng = np.random.default_rng(rng_seed)
     s = e.slots
@@ -239,6 +266,13 @@ def speculative_gemvs(e, seed=1234, rng_seed=53, plan=None, taken=None):
         for x in (xd, ud):
             e.free(x)
         res.append(e.decrypt(du, sk))
+        if plain is not None:
+            z1 = zz[1] + zz[4] if kind == "clobber" else zz[1]
+            pxd = zz[2] - z1 if kind == "swap" else z1 - zz[2]
+            pud = zz[3] - zz[4]
+            pya = M3 @ pud if kind == "realias" else Ma @ pxd
+            pyb = pya if kind == "one" else M2 @ pud
+            note(plain, res, zz[0] - (pya + pyb))
         for x in cts:
             e.free(x)
         if taken is not None and hasattr(e.lib, "gpqhe_spec_gemv_taken"):

@@ -135,9 +135,13 @@ def inputs(e, pk, lvl, rng):
 @pytest.mark.parametrize("name", list(CONTEXTS))
 def test_exact_key_switch(oracle, name, logn):
     """he_mul, he_mul + he_rescale, he_mul_rescale and he_rot(1), he_rot(slots - 1)
-    equal the integer restatement on every output word, at level L and one
-    level down, on genuine ciphertexts and on constructed c1 (all limbs q - 1;
-    all y_i = f_i - 1, where the conversion overshoots by alpha - 1)."""
+    equal the integer restatement on every output word, at every level L ... 1
+    (every ndig and every size of the last digit the chain has; he_rescale and
+    he_mul_rescale from level 2, the lowest with a limb to drop), on genuine
+    ciphertexts and on constructed c1 (all limbs q - 1; all y_i = f_i - 1,
+    where the conversion overshoots by alpha - 1).  The GPU level sweep
+    (tests/test_gpu_levels.py) compares the product with this oracle at the
+    same levels."""
     e = ctx(oracle, name, logn)
     L, n = e.L, e.n
     model = M.HybridModel(e.primes, L, e.info.alpha)
@@ -154,20 +158,17 @@ def test_exact_key_switch(oracle, name, logn):
     rng = np.random.default_rng(logn)
     a, b, out = e.ct(), e.ct(), e.ct()
     seen_overshoot = 0
-    for lvl in (L, L - 1):
+    for lvl in range(L, 0, -1):
         for label, pa, pb in inputs(e, pk, lvl, rng):
             where = (name, logn, lvl, label)
             # he_moddown only drops the top limb: import at L, then step down
-            if lvl == L:
-                e.import_(a, pa, L, scale=2.0 ** 30)
-                e.import_(b, pb, L, scale=2.0 ** 30)
-            else:
-                top = np.zeros((2, 1, n), dtype=np.uint64)
-                e.import_(a, np.concatenate([pa, top], axis=1), L, scale=2.0 ** 30)
-                e.import_(b, np.concatenate([pb, top], axis=1), L, scale=2.0 ** 30)
+            top = np.zeros((2, L - lvl, n), dtype=np.uint64)
+            e.import_(a, np.concatenate([pa, top], axis=1), L, scale=2.0 ** 30)
+            e.import_(b, np.concatenate([pb, top], axis=1), L, scale=2.0 ** 30)
+            for _ in range(L - lvl):
                 e.moddown(a)
                 e.moddown(b)
-            assert a.nlimbs == lvl
+            assert a.nlimbs == lvl and b.nlimbs == lvl
             ca, cb = coef(e, pa), coef(e, pb)
             for lo, hi in model.digits(lvl):
                 F = 1
@@ -185,6 +186,8 @@ def test_exact_key_switch(oracle, name, logn):
             e.mul(out, a, b, rlk)
             want = model.mul(ca, cb, rlk_c)
             assert out.nlimbs == lvl and np.array_equal(e.export(out), words(e, want)), where + ("mul",)
+            if lvl < 2:
+                continue  # one limb: nothing to rescale away
             e.rescale(out)
             want = model.rescale(want)
             assert out.nlimbs == lvl - 1 and np.array_equal(e.export(out), words(e, want)), where + ("rescale",)
